@@ -11,6 +11,11 @@ in HBM when the timed region starts. value = env steps of all ranks / max-over-r
 Multi-GPU: one process per GPU (torch.distributed.run); the reference shards num_envs over ranks
 (num_envs_per_device = num_envs / world_size, ac:399), gradients are averaged with RCCL every
 minibatch — strong scaling by default, --scaling weak keeps num_envs per GPU.
+
+A plain run does only what the headline needs: set up, --warmup iterations, --steps timed iterations,
+the JSON line (with the roofline of the dominant kernel, from HIP events inside the timed region).
+--full adds the legs that take runs of their own (dW's event fraction, the fp32-MFMA leg, the CLI's
+SPS, the CPU baseline); --dump-outputs DIR writes what the last timed iteration computed.
 """
 import argparse
 import json
@@ -198,6 +203,46 @@ def fp32_leg(cfg, E, args, work):
         tr.close()
 
 
+DUMP_SAMPLE_SEED = 0
+DUMP_MAX_ROWS = 1 << 20        # per-row scalars ([T, E] buffers): at most 4 MiB each
+DUMP_MAX_WIDE_ROWS = 1 << 16   # obs / actions rows ([T, E, O] / [T, E, A])
+
+
+def dump_rows(B):
+    """Row indices of a [B] / [B, width] storage buffer that --dump-outputs writes: all of them up to
+    the caps, else a seeded sample without replacement, sorted; the wide rows are a subset of the rows."""
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    rows = np.sort(rng.choice(B, DUMP_MAX_ROWS, replace=False)) if B > DUMP_MAX_ROWS else np.arange(B)
+    wide = np.sort(rng.choice(rows, DUMP_MAX_WIDE_ROWS, replace=False)) if rows.size > DUMP_MAX_WIDE_ROWS else rows
+    return rows, wide
+
+
+def dump_outputs(tr, out_dir):
+    """--dump-outputs: what the last timed iteration left for its caller, as <name>.npy (float32):
+    the agent parameters and Adam moments after the update, the [T, E, *] rollout storage the update
+    read (obs, actions, logprobs, rewards, dones, values, advantages, returns) and the env state the
+    next iteration starts from (next_obs, next_done). Storage larger than the row caps above is
+    written as a fixed, seeded sample of its T*E rows (sorted, the same rows in every buffer and
+    every run), so the whole dump stays below 64 MB at any --num-envs / --num-steps."""
+    os.makedirs(out_dir, exist_ok=True)
+    ag, h = tr.agent, tr.hcfg
+    T, E, O_, A = h.num_steps, h.num_envs, h.obs_dim, h.act_dim
+    ag.sync()
+    m, v, _ = ag.adam_state()
+    arrays = {"params": ag.params(), "adam_m": m, "adam_v": v,
+              "next_obs": tr.next_obs.numpy(), "next_done": tr.next_done.numpy()}
+    B = T * E
+    rows, wide = dump_rows(B)
+    for name, which, width in (("obs", ppo_amd.BUF_OBS, O_), ("actions", ppo_amd.BUF_ACTIONS, A),
+                               ("logprobs", ppo_amd.BUF_LOGPROBS, 0), ("rewards", ppo_amd.BUF_REWARDS, 0),
+                               ("dones", ppo_amd.BUF_DONES, 0), ("values", ppo_amd.BUF_VALUES, 0),
+                               ("advantages", ppo_amd.BUF_ADVANTAGES, 0), ("returns", ppo_amd.BUF_RETURNS, 0)):
+        a = ag.buffer(which, (B, width) if width else (B,)).numpy()
+        arrays[name] = a[wide] if width else a[rows]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -231,11 +276,19 @@ def main():
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--num-steps", type=int, default=128)
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also run the legs beside the headline: dW's HIP-event "
+                         "fraction (roofline.dw), the fp32-MFMA leg, the CLI's own SPS and the CPU baseline. "
+                         "Off by default: a plain run sets up, warms up, times --steps iterations and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--profile-all", action="store_true", help="HIP-event time every kernel class")
-    ap.add_argument("--no-cli", action="store_true", help="skip the ac_ppo_continuous_action CLI SPS run")
+    ap.add_argument("--no-cli", action="store_true",
+                    help="with --full: skip the ac_ppo_continuous_action CLI SPS run")
     ap.add_argument("--no-fp32-leg", action="store_true",
-                    help="skip the second timed run with every GEMM on fp32 MFMAs (upd_mfma=16,dw_mfma=f32)")
+                    help="with --full: skip the second timed run with every GEMM on fp32 MFMAs "
+                         "(upd_mfma=16,dw_mfma=f32)")
     ap.add_argument("--cli-iterations", type=int, default=30)
     ap.add_argument("--comm", choices=["rccl", "host"], default="rccl",
                     help="N > 1 data path: RCCL (one GPU per rank), or the host transport over gloo with every "
@@ -333,10 +386,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)  # before anything below iterates again
+
     units = E_total * T * args.steps
     value = units / elapsed
     dw_prof = None
-    if world == 1 and not args.profile_all:
+    if args.full and world == 1 and not args.profile_all:
         # dW's own fraction beside k_upd's: a few iterations after the timed region with HIP events
         # around the dW launches too (kept out of the timed region so it carries one event class only)
         tr.agent.profile_reset()
@@ -415,8 +471,7 @@ def main():
             "data": "synthetic: device-resident HalfCheetah-shaped env (O=17, A=6), random-init AC agent",
             "config": {"workload": f"ac_ppo_continuous_action HalfCheetah-v5 num_envs={E_total} num_steps={T} "
                                    f"num_minibatches={cfg.num_minibatches} update_epochs={cfg.update_epochs}",
-                       "num_envs": E_total, "num_envs_per_device": E, "num_steps": T,
-                       "minibatch_per_device": E * T // cfg.num_minibatches, "parallelism": f"dp{world}",
+                       "num_envs": E_total, "num_envs_per_device": E, "num_steps": T,                       "minibatch_per_device": E * T // cfg.num_minibatches, "parallelism": f"dp{world}",
                        "comm_ranks": comm_world, "comm_kind": comm_kind,
                        "devices": [d for d, _ in devices], "device_pci_bus_ids": [b for _, b in devices],
                        **({"comm": "host transport (gloo), all ranks on GPU 0: rehearsal, not a scaling number"}
@@ -427,16 +482,17 @@ def main():
             out["kernels_ms_per_step"] = {k: round(v[0] / args.steps, 3) for k, v in prof.items()}
             out["kernels_ms_note"] = ("HIP-event pairs around every kernel class: the sum can exceed ms_per_step "
                                       "(each pair adds its own overhead to the class it brackets)")
-    if world == 1 and not args.no_fp32_leg:
-        # the same workload with every GEMM on fp32 MFMAs (no split-bf16 piece products)
-        tr.close()
-        tr = None
-        out["fp32_mfma"] = fp32_leg(cfg, E, args, algorithmic_work(17, 6, 256, E, T, cfg.num_minibatches, 12))
-    if rank == 0:
-        if world == 1 and not args.no_cli:
+    if args.full and world == 1:
+        if not args.no_fp32_leg:
+            # the same workload with every GEMM on fp32 MFMAs (no split-bf16 piece products)
+            tr.close()
+            tr = None
+            out["fp32_mfma"] = fp32_leg(cfg, E, args, algorithmic_work(17, 6, 256, E, T, cfg.num_minibatches, 12))
+        if not args.no_cli:
             out["cli_value"] = cli_sps(E_total, T, args.cli_iterations)
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(E, T, cfg.num_minibatches, cfg.update_epochs)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if tr is not None:
         tr.close()

@@ -300,6 +300,12 @@ static float gamma_mt(float alpha, uint64_t seed, int rank, long env, long step,
   return d;
 }
 
+/* at::_sample_dirichlet's clamp of the Beta sample to [FLT_MIN, nextafter(1, 0)] (beta_sample01 in
+ * ppo_device.hpp): keeps log(1 - s) finite when the quotient rounds to 1. */
+static float beta_sample01(float ga, float gb) {
+  return fminf(fmaxf(ga / (ga + gb), 1.17549435e-38f), 0.99999994f);
+}
+
 void orc_normal_noise(uint64_t seed, int rank, long env, long step, int A, float* z) {
   for (int a = 0; a < A; ++a) {
     uint32_t rr[4];
@@ -313,7 +319,7 @@ void orc_normal_noise(uint64_t seed, int rank, long env, long step, int A, float
 float orc_beta_sample01(float alpha, float beta, uint64_t seed, int rank, long env, long step, int a) {
   const float ga = gamma_mt(alpha, seed, rank, env, step, 0x10000u + (uint32_t)(a * 2 + 0) * 64u);
   const float gb = gamma_mt(beta, seed, rank, env, step, 0x10000u + (uint32_t)(a * 2 + 1) * 64u);
-  return ga / (ga + gb);
+  return beta_sample01(ga, gb);
 }
 
 void orc_get_action_and_value(const ppo_layout* L, const float* P, int n, const float* x, int mode,
@@ -368,7 +374,7 @@ void orc_get_action_and_value(const ppo_layout* L, const float* P, int n, const 
         } else {
           float ga = gamma_mt(al, seed, rank, env, step_id, 0x10000u + (uint32_t)(a * 2 + 0) * 64u);
           float gb = gamma_mt(be, seed, rank, env, step_id, 0x10000u + (uint32_t)(a * 2 + 1) * 64u);
-          s = ga / (ga + gb);
+          s = beta_sample01(ga, gb);
         }
         float ab = al + be;
         float l = xlogy_f(al - 1.0f, s) + xlogy_f(be - 1.0f, 1.0f - s);
@@ -839,7 +845,7 @@ void orc_carla_forward(const ppo_carla_layout* L, const float* P, float beta_min
       } else {                                                  /* Dirichlet sample, Philox contract */
         const float ga = gamma_mt(al, seed, rank, env, step_id, 0x10000u + (uint32_t)(a * 2 + 0) * 64u);
         const float gb = gamma_mt(be, seed, rank, env, step_id, 0x10000u + (uint32_t)(a * 2 + 1) * 64u);
-        s = ga / (ga + gb);
+        s = beta_sample01(ga, gb);
       }
       const float ab = al + be;
       float l = xlogy_f(al - 1.0f, s) + xlogy_f(be - 1.0f, 1.0f - s);

@@ -266,7 +266,7 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
       } else if (a.mode == PPO_MEAN) {
         sv = al / (al + be);
       } else {
-        sv = ia[1] / (ia[1] + ib[1]);
+        sv = beta_sample01(ia[1], ib[1]);
       }
       const float ab = al + be;
       float lgab, psab, tab_unused;

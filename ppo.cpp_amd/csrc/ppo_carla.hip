@@ -881,7 +881,7 @@ PPO_DEV void beta_action(const HeadArgs& h, int r, int ai, const BetaConc& ca, c
     else if (al > 1.0f && be <= 1.0f) sv = 1.0f;
     else sv = al / (al + be);
   } else {
-    sv = ca.draw / (ca.draw + cb.draw);
+    sv = beta_sample01(ca.draw, cb.draw);
   }
   sv = opaque_(sv);
   const float ab = al + be;

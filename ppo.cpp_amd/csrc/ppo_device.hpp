@@ -115,6 +115,14 @@ PPO_DEV float gamma_mt_d0(float alpha, GammaDraw d0, SampleKey k, long env, long
   return d;
 }
 
+// Beta(alpha, beta) sample in (0, 1) from its two gamma draws. at::_sample_dirichlet, which the
+// reference's Beta samples through, clamps ga / (ga + gb) to [FLT_MIN, nextafter(1, 0)]: with a
+// concentrated policy the quotient rounds to 1.0f, whose log-prob term (beta - 1) * log(1 - s) is
+// -inf and turns the next update's gradient, and with it every parameter, to NaN.
+PPO_DEV float beta_sample01(float ga, float gb) {
+  return fminf(fmaxf(ga / (ga + gb), 1.17549435e-38f), 0.99999994f);
+}
+
 // Feistel permutation of [0,B) keyed by (seed, rank, epoch counter); replaces torch::randperm
 // (ppo:490, ac:804). Mirrors orc_perm_index.
 struct PermKey {

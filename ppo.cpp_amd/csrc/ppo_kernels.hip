@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64) void k_act(ActArgs a) {
         } else {
           const float ga = gamma_mt(al, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 0) * 64u);
           const float gb = gamma_mt(be, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 1) * 64u);
-          s = ga / (ga + gb);
+          s = beta_sample01(ga, gb);
         }
         const float ab = al + be;
         const float lga = lgammaf(al), lgb = lgammaf(be), lgab = lgammaf(ab);
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void k_act2(ActArgs a) {
       } else {
         const float ga = gamma_mt(al, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 0) * 64u);
         const float gb = gamma_mt(be, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 1) * 64u);
-        sv = ga / (ga + gb);
+        sv = beta_sample01(ga, gb);
       }
       const float ab = al + be;
       const float lga = lgammaf(al), lgb = lgammaf(be), lgab = lgammaf(ab);

@@ -363,7 +363,7 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
       const float* ia = ITM + (idx * 2 + 0) * 4;
       const float* ib = ITM + (idx * 2 + 1) * 4;
       const float al = ia[0], be = ib[0];
-      const float s01 = ia[1] / (ia[1] + ib[1]);
+      const float s01 = beta_sample01(ia[1], ib[1]);
       const float act = (s01 - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
       ACT[r * 24 + ai] = act;
       if (e < E) a.s_actions[((long)t * E + e) * A + ai] = act;
@@ -1389,7 +1389,7 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
       if (bitem < R * A * 2 && (bitem & 1) == 0) {
         const int ra = bitem >> 1, r = ra / A, ai = ra - r * A, e = row0 + r;
         const float al = bc, be = pc;
-        const float s01 = bg / (bg + pg);
+        const float s01 = beta_sample01(bg, pg);
         const float act = (s01 - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
         ACT[r * 24 + ai] = act;
         if (e < E) {

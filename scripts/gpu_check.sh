@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --t
 tail -2 $OUT/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo "smoke failed"; tail -30 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 400 python bench.py > $OUT/bench_default.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench_default.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench_default.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench_default.log; exit 1; }
 tail -1 $OUT/bench_default.log
 timeout -k 10 300 python bench.py --steps 5 --warmup 1 --profile-all --no-cpu-baseline > $OUT/bench_all.log 2>&1 || { echo "bench profile-all failed"; tail -30 $OUT/bench_all.log; exit 1; }
 tail -1 $OUT/bench_all.log

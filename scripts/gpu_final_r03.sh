@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 bash $R/scripts/gpu_r03.sh $TAG || exit 1
 cd $R
-timeout -k 10 400 python bench.py > $OUT/bench_default.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench_default.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench_default.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench_default.log; exit 1; }
 tail -1 $OUT/bench_default.log | cut -c1-800
 timeout -k 10 300 python bench.py --steps 10 --warmup 2 --profile-all --no-cpu-baseline --no-cli > $OUT/bench_all.log 2>&1 || { echo "bench profile-all failed"; exit 1; }
 bash $R/scripts/gpu_profile.sh $TAG > $OUT/profile.txt 2>&1 || { echo "profile failed"; tail -5 $OUT/profile.txt; exit 1; }

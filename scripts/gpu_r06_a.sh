@@ -15,5 +15,5 @@ timeout -k 10 600 python -u -m pytest -x -v -p no:cacheprovider --timeout 300 --
   tests/test_bench_gpu.py::test_bench_single_rank_line > $OUT/tests.txt 2>&1 || { echo "tests failed"; tail -40 $OUT/tests.txt; exit 1; }
 tail -3 $OUT/tests.txt
 grep -E "max \|adv" $OUT/tests.txt | head
-timeout -k 10 400 python bench.py --no-cli --no-cpu-baseline > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cli --no-cpu-baseline > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -30 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-2500

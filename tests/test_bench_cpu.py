@@ -23,6 +23,25 @@ def test_bench_import_does_not_load_the_library():
     assert bench.ppo_amd is None
 
 
+def test_dump_rows_are_a_fixed_sorted_sample_within_the_caps():
+    """--dump-outputs: every row below the caps, above them the same sorted sample in every run, and
+    the caps keep a dump of the eight storage buffers (O=17, A=6) below 64 MB."""
+    import numpy as np
+    rows, wide = bench.dump_rows(8192)
+    assert np.array_equal(rows, np.arange(8192)) and np.array_equal(wide, rows)
+    rows, wide = bench.dump_rows(4096 * 128)  # the metric config: scalars whole, obs / actions sampled
+    assert np.array_equal(rows, np.arange(4096 * 128)) and wide.size == bench.DUMP_MAX_WIDE_ROWS
+    B = 3 * bench.DUMP_MAX_ROWS + 5
+    rows, wide = bench.dump_rows(B)
+    assert rows.size == bench.DUMP_MAX_ROWS and wide.size == bench.DUMP_MAX_WIDE_ROWS
+    for a in (rows, wide):
+        assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < B
+    assert np.isin(wide, rows).all()
+    again = bench.dump_rows(B)
+    assert np.array_equal(rows, again[0]) and np.array_equal(wide, again[1])
+    assert 4 * (6 * bench.DUMP_MAX_ROWS + (17 + 6) * bench.DUMP_MAX_WIDE_ROWS) < 40e6
+
+
 def test_world_size_mismatch_fails_loudly():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"],

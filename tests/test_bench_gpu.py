@@ -18,7 +18,7 @@ def last_json(out):
 
 
 def test_bench_single_rank_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
                         "--no-cli", "--no-cpu-baseline", "--num-envs", "512"], capture_output=True, text=True,
                        timeout=300, cwd=ROOT, check=True)
     d = last_json(r.stdout)
@@ -35,6 +35,56 @@ def test_bench_single_rank_line():
     assert f["options"] == "upd_mfma=16,dw_mfma=f32" and f["value"] > 0 and "bx" not in f["kernels"]
     assert 0 < f["fwdbwd"]["frac"] < 1
     assert 0 < roof["dw"]["frac"] < 2 and roof["dw"]["launches"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and the timed region's roofline only, and
+    --dump-outputs writes the last timed iteration's results as float32 .npy files."""
+    import numpy as np
+    E, T, O_, A = 64, 128, 17, 6
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--num-envs", str(E), "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT, check=True)
+    d = last_json(r.stdout)
+    for k in KEYS:
+        assert k in d, k
+    assert d["steps"] == 2 and d["dtype"] == "f32" and d["higher_is_better"] is True and d["unit"] == "env_steps/s"
+    assert abs(d["value"] - E * T / (d["ms_per_step"] / 1e3)) / d["value"] < 0.01
+    for k in ("fp32_mfma", "cli_value", "cpu_baseline"):
+        assert k not in d, k
+    assert d["roofline"]["kernel"] == "fwdbwd" and "dw" not in d["roofline"]
+    shapes = {"params": None, "adam_m": None, "adam_v": None, "next_obs": (E, O_), "next_done": (E,),
+              "obs": (T * E, O_), "actions": (T * E, A), "logprobs": (T * E,), "rewards": (T * E,), "dones": (T * E,),
+              "values": (T * E,), "advantages": (T * E,), "returns": (T * E,)}
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == sorted(n + ".npy" for n in shapes)
+    total = 0
+    for n, shape in shapes.items():
+        a = np.load(tmp_path / "out" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        assert shape is None or a.shape == shape, (n, a.shape)
+        total += a.nbytes
+    arrs = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("params", "adam_m", "adam_v", "actions", "returns")}
+    assert arrs["params"].shape == arrs["adam_m"].shape == arrs["adam_v"].shape
+    assert np.abs(arrs["adam_m"]).max() > 0 and (arrs["adam_v"] >= 0).all()  # optimizer steps were taken
+    assert np.abs(arrs["actions"]).max() <= 1.0 and arrs["returns"].std() > 0
+    assert total <= 64e6
+
+
+def test_bench_long_run_keeps_finite_outputs(tmp_path):
+    """The step count of a measurement is chosen by ms_per_step, so it can be hundreds. As the Beta
+    policy concentrates, a sample ga / (ga + gb) rounds to 1.0f; unclamped its log-prob is -inf and
+    the next update turns every parameter to NaN (seen at this size within 250 iterations, at the
+    metric size within 30-110). With at::_sample_dirichlet's clamp (beta_sample01) every dumped
+    array of a 300-step run is finite."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "300", "--warmup", "3",
+                        "--num-envs", "256", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT, check=True)
+    d = last_json(r.stdout)
+    assert d["steps"] == 300
+    for f in os.listdir(tmp_path / "out"):
+        assert np.isfinite(np.load(tmp_path / "out" / f)).all(), f
 
 
 def test_bench_one_rank_rccl_reports_its_device():

@@ -46,6 +46,22 @@ def test_ac_act_given_and_mean():
     np.testing.assert_allclose(lpm, d["mean_logprob"], rtol=1e-5, atol=2e-5)
 
 
+def test_beta_sample_stays_inside_the_open_interval():
+    """at::_sample_dirichlet clamps the sample to [FLT_MIN, nextafter(1, 0)]. With alpha = 1e6 and
+    beta = 1 the quotient ga / (ga + gb) rounds to 1.0f for about 3 % of the draws (gb < 2^-25 * 1e6
+    = 0.03, gb ~ Exp(1)), so among 2000 draws the clamp is exercised some 60 times; the same holds mirrored for alpha = 1."""
+    import ctypes as C
+    f = O.lib().orc_beta_sample01
+    f.restype = C.c_float
+    f.argtypes = [C.c_float, C.c_float, C.c_uint64, C.c_int, C.c_long, C.c_long, C.c_int]
+    top = np.nextafter(np.float32(1), np.float32(0))
+    hi = np.array([f(1e6, 1.0, 1, 0, e, 0, 0) for e in range(2000)], np.float32)
+    lo = np.array([f(1.0, 1e6, 1, 0, e, 0, 0) for e in range(2000)], np.float32)
+    assert hi.max() == top and (hi == top).sum() > 20 and hi.min() > 0.999
+    assert lo.min() >= np.finfo(np.float32).tiny and lo.max() < 1e-3 and (lo > 0).all()
+    assert np.isfinite(np.log1p(-hi.astype(np.float32))).all()
+
+
 def test_beta_distribution_spot_values():
     _, d = load_case("beta_dist")
     lib = O.lib()
