@@ -25,6 +25,14 @@
  * linear.{0,2}, state_linear.{0,2}, value_head.{0,2,4}, policy_head.{0,2}, dist_mu.0,
  * dist_sigma.0 (registration order, carla_model.h:108-192). Conv weights [OC, IC, k, k],
  * Linear weights [out, in].
+ *
+ * The reference's LayerNorm variants (image_encoder "roach_ln", :44-64: a LayerNorm over [C, H, W]
+ * after every convolution; use_layer_norm, :113-175: a LayerNorm before every ReLU of the four MLPs,
+ * the policy head's under use_layer_norm_policy_head) are a ppo_carla_arch given to
+ * ppo_carla_create2; their tensors are described by ppo_carla_layout2 (cnn.{3i} / cnn.{3i+1},
+ * linear.{0,1,3,4}, ..., value_head.{0,1,3,4,6}). Everything above — ppo_carla_layout,
+ * ppo_carla_create(_ex), the default agent's kernels and results — is unchanged by them.
+ * "roach_ln2" and use_positional_encoding are not built.
  */
 #ifndef PPO_CARLA_H
 #define PPO_CARLA_H
@@ -110,6 +118,111 @@ static inline int ppo_carla_layout_init(ppo_carla_layout* L, int C, int IH, int 
   return 0;
 }
 
+/* ---- LayerNorm variants (carla_model.h:44-64 image_encoder "roach_ln", :113-175 use_layer_norm) ----
+ * All zero is the agent above. encoder_ln: a LayerNorm over [C, H, W] after every convolution
+ * (cnn.{3i} conv, cnn.{3i+1} LayerNorm, cnn.{3i+2} ReLU); mlp_ln: a LayerNorm before every ReLU of
+ * linear, state_linear and value_head (Linear at 0 / 3 / 6, LayerNorm at 1 / 4); policy_ln
+ * (use_layer_norm_policy_head, read only when mlp_ln is set): the same for policy_head.
+ * nn::LayerNorm defaults: biased variance, eps 1e-5, elementwise affine weight / bias of the
+ * normalised shape. */
+typedef struct ppo_carla_arch { int encoder_ln; int mlp_ln; int policy_ln; } ppo_carla_arch;
+
+#define PPO_CARLA_MAX_TENSORS2 64
+
+/* ppo_carla_layout plus the offsets of the LayerNorm weight (gamma) / bias (beta) tensors (-1 where
+ * the arch has none). t_off / t_len / t_grad stay in named_parameters() order. */
+typedef struct ppo_carla_layout2 {
+  int C, IH, IW, NM, NV, A;
+  long P;
+  long hi, lo;
+  long conv_w[PPO_CARLA_NCONV], conv_b[PPO_CARLA_NCONV];
+  int conv_ic[PPO_CARLA_NCONV], conv_oc[PPO_CARLA_NCONV], conv_k[PPO_CARLA_NCONV], conv_s[PPO_CARLA_NCONV];
+  int conv_ih[PPO_CARLA_NCONV], conv_iw[PPO_CARLA_NCONV], conv_oh[PPO_CARLA_NCONV], conv_ow[PPO_CARLA_NCONV];
+  long lin_w[2], lin_b[2];
+  long st_w[2], st_b[2];
+  long v_w[3], v_b[3];
+  long pi_w[2], pi_b[2];
+  long mu_w, mu_b, sg_w, sg_b;
+  ppo_carla_arch arch;          /* policy_ln normalised to 0 when mlp_ln is 0 */
+  long conv_g[PPO_CARLA_NCONV], conv_be[PPO_CARLA_NCONV];  /* cnn.{3i+1}: [OC, OH, OW] */
+  long lin_g[2], lin_be[2];     /* linear.{1,4}: [512], [256] */
+  long st_g[2], st_be[2];       /* state_linear.{1,4}: [256] */
+  long v_g[2], v_be[2];         /* value_head.{1,4}: [256] */
+  long pi_g[2], pi_be[2];       /* policy_head.{1,4}: [256] */
+  int ntensors;
+  long t_off[PPO_CARLA_MAX_TENSORS2];
+  long t_len[PPO_CARLA_MAX_TENSORS2];
+  int t_grad[PPO_CARLA_MAX_TENSORS2];
+} ppo_carla_layout2;
+
+static inline long ppo_carla__add2(ppo_carla_layout2* L, long* cur, long n, int grad) {
+  const long off = *cur;
+  L->t_off[L->ntensors] = off;
+  L->t_len[L->ntensors] = n;
+  L->t_grad[L->ntensors] = grad;
+  L->ntensors++;
+  *cur += n;
+  return off;
+}
+
+/* Returns 0; -1 as ppo_carla_layout_init; -2 if arch->encoder_ln is set with a bev other than
+ * 192 x 192 (the reference hard-codes roach_ln's LayerNorm shapes, carla_model.h:45-62). arch NULL
+ * = all zero. */
+static inline int ppo_carla_layout2_init(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
+                                         const ppo_carla_arch* arch) {
+  static const int oc[PPO_CARLA_NCONV] = {8, 16, 32, 64, 128, 256};
+  static const int ks[PPO_CARLA_NCONV] = {5, 5, 5, 3, 3, 3};
+  static const int st[PPO_CARLA_NCONV] = {2, 2, 2, 2, 2, 1};
+  long cur = 0;
+  int i, h = IH, w = IW, ic = C;
+  const int eln = arch && arch->encoder_ln, mln = arch && arch->mlp_ln, pln = mln && arch->policy_ln;
+  if (C <= 0 || IH <= 0 || IW <= 0 || NM <= 0 || NV < 0 || A <= 0) return -1;
+  if (eln && (IH != 192 || IW != 192)) return -2;
+  L->C = C; L->IH = IH; L->IW = IW; L->NM = NM; L->NV = NV; L->A = A;
+  L->arch.encoder_ln = eln; L->arch.mlp_ln = mln; L->arch.policy_ln = pln;
+  L->ntensors = 0;
+  L->hi = ppo_carla__add2(L, &cur, 1, 0);
+  L->lo = ppo_carla__add2(L, &cur, 1, 0);
+  for (i = 0; i < PPO_CARLA_NCONV; ++i) {
+    L->conv_ic[i] = ic; L->conv_oc[i] = oc[i]; L->conv_k[i] = ks[i]; L->conv_s[i] = st[i];
+    L->conv_ih[i] = h; L->conv_iw[i] = w;
+    if (h < ks[i] || w < ks[i]) return -1;
+    h = (h - ks[i]) / st[i] + 1;
+    w = (w - ks[i]) / st[i] + 1;
+    L->conv_oh[i] = h; L->conv_ow[i] = w;
+    L->conv_w[i] = ppo_carla__add2(L, &cur, (long)oc[i] * ic * ks[i] * ks[i], 1);
+    L->conv_b[i] = ppo_carla__add2(L, &cur, oc[i], 1);
+    L->conv_g[i] = eln ? ppo_carla__add2(L, &cur, (long)oc[i] * h * w, 1) : -1;
+    L->conv_be[i] = eln ? ppo_carla__add2(L, &cur, (long)oc[i] * h * w, 1) : -1;
+    ic = oc[i];
+  }
+  if (256L * h * w != 1024) return -1;
+#define PPO_CARLA__LIN(W, B, G, BE, k, nw, nb, ln)                                   \
+  L->W[k] = ppo_carla__add2(L, &cur, (nw), 1); L->B[k] = ppo_carla__add2(L, &cur, (nb), 1); \
+  L->G[k] = (ln) ? ppo_carla__add2(L, &cur, (nb), 1) : -1; L->BE[k] = (ln) ? ppo_carla__add2(L, &cur, (nb), 1) : -1
+  PPO_CARLA__LIN(lin_w, lin_b, lin_g, lin_be, 0, 512L * (1024 + 256), 512, mln);
+  PPO_CARLA__LIN(lin_w, lin_b, lin_g, lin_be, 1, 256L * 512, 256, mln);
+  PPO_CARLA__LIN(st_w, st_b, st_g, st_be, 0, 256L * NM, 256, mln);
+  PPO_CARLA__LIN(st_w, st_b, st_g, st_be, 1, 256L * 256, 256, mln);
+  PPO_CARLA__LIN(v_w, v_b, v_g, v_be, 0, 256L * (256 + NV), 256, mln);
+  PPO_CARLA__LIN(v_w, v_b, v_g, v_be, 1, 256L * 256, 256, mln);
+  L->v_w[2] = ppo_carla__add2(L, &cur, 256, 1); L->v_b[2] = ppo_carla__add2(L, &cur, 1, 1);
+  PPO_CARLA__LIN(pi_w, pi_b, pi_g, pi_be, 0, 256L * 256, 256, pln);
+  PPO_CARLA__LIN(pi_w, pi_b, pi_g, pi_be, 1, 256L * 256, 256, pln);
+#undef PPO_CARLA__LIN
+  L->mu_w = ppo_carla__add2(L, &cur, 256L * A, 1); L->mu_b = ppo_carla__add2(L, &cur, A, 1);
+  L->sg_w = ppo_carla__add2(L, &cur, 256L * A, 1); L->sg_b = ppo_carla__add2(L, &cur, A, 1);
+  L->P = cur;
+  return 0;
+}
+
+/* the exported form of ppo_carla_layout2_init (bindings); the message names the reason */
+int ppo_carla_layout2_fill(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
+                           const ppo_carla_arch* arch);
+/* named_parameters() name of tensor t ("cnn.1.weight", ...) into buf (NUL-terminated, truncated to
+ * len); returns 0, -1 for a bad index or buffer */
+int ppo_carla_tensor_name(const ppo_carla_layout2* L, int t, char* buf, int len);
+
 typedef struct ppo_carla_config {
   int obs_channels;            /* 15 */
   int bev_h, bev_w;            /* 192, 192 */
@@ -155,6 +268,15 @@ int ppo_carla_create(const ppo_carla_config* cfg, int device, ppo_carla_t** out)
 int ppo_carla_create_ex(const ppo_carla_config* cfg, int device, const char* options, ppo_carla_t** out);
 int ppo_carla_destroy(ppo_carla_t* c);
 int ppo_carla_get_layout(const ppo_carla_t* c, ppo_carla_layout* out);
+/* ppo_carla_create_ex with an architecture (arch NULL = all zero = ppo_carla_create_ex). Refused
+ * before any HIP call: encoder_ln with a bev other than 192 x 192, and an explicit tail=fused or
+ * tail=staged with any LayerNorm (such an agent always runs the per-layer forward, one k_carla_ln
+ * after each normalised layer). roach_ln2 and use_positional_encoding are not built.
+ * ppo_carla_get_layout2 serves every agent (the default one's offsets are ppo_carla_layout's);
+ * ppo_carla_get_layout fails on a LayerNorm agent, whose tensors it cannot describe. */
+int ppo_carla_create2(const ppo_carla_config* cfg, const ppo_carla_arch* arch, int device, const char* options,
+                      ppo_carla_t** out);
+int ppo_carla_get_layout2(const ppo_carla_t* c, ppo_carla_layout2* out);
 /* host floats in named_parameters() order (torch::load of a model_*.pth, ac_ppo_carla.cpp) */
 int ppo_carla_load_params(ppo_carla_t* c, const float* host, long n);
 /* AgentImpl::forward (carla_model.h:270-318) for n rows; every array is a device pointer:
@@ -198,6 +320,19 @@ int ppo_carla_last_grad(ppo_carla_t* c, float* host, long n);
 /* Adam moments in the same flat order, and the step count */
 int ppo_carla_save_adam(ppo_carla_t* c, float* m_host, float* v_host, long n, long* step);
 int ppo_carla_load_adam(ppo_carla_t* c, const float* m_host, const float* v_host, long n, long step);
+
+/* ---- test hooks: the LayerNorm launches of the agent on caller arrays (device pointers) ----------
+ * forward: y[r, 0..F) = relu(layer_norm(z[r, 0..F)) * gamma + beta) for n rows of strides in_stride /
+ * out_stride, stat[r] = {mean, rstd} (k_carla_ln; k_carla_ln_big for rows of 4 096 floats and more).
+ * backward: dz [n, F] (dense) from dy (dense [n, F]), the ReLU mask y > 0 and the forward's z / stat;
+ * dgamma / dbeta [F]. The agent's own backward receives dy already masked by the consuming layer's
+ * input-gradient kernel; the hook applies that mask with one extra launch, then runs the agent's
+ * column pass (k_carla_ln_dgb + k_carla_ln_dgb_sum) and row pass (k_carla_ln_bwd). */
+int ppo_carla_debug_ln_forward(int n, int F, const float* z, long in_stride, const float* gamma, const float* beta,
+                               float* y, long out_stride, float* stat, void* stream);
+int ppo_carla_debug_ln_backward(int n, int F, const float* z, long in_stride, const float* gamma, const float* stat,
+                                const float* y, long out_stride, const float* dy, float* dz, float* dgamma,
+                                float* dbeta, void* stream);
 
 /* ---- data parallelism (ac_ppo_carla.cpp:243, 561-616; torchfort::Comm, distributed.cpp:81-224) ----
  * One RCCL communicator per agent; id from ppo_comm_unique_id (ppo_hip.h), PPO_COMM_ID_BYTES bytes.

@@ -15,7 +15,8 @@
  * module structure written around them (Sequential children, parameterless Tanh / ReLU modules,
  * class numbering) is the reference agents' (ppo_continuous_action.cpp:120-157,
  * ac_ppo_continuous_action.cpp:150-249, carla_model.h:65-192 with image_encoder "roach" and
- * use_layer_norm false). Loading requires every named parameter with the same shape, as
+ * use_layer_norm false; ppo_carla_pth_*2: also "roach_ln" and use_layer_norm). Loading requires
+ * every named parameter with the same shape, as
  * torch::load does; extra entries are ignored.
  */
 #ifndef PPO_PTH_H
@@ -47,6 +48,12 @@ int ppo_pth_load_adam(const ppo_layout* L, const char* path, float* m, float* v,
 
 int ppo_carla_pth_save(const ppo_carla_layout* L, const float* params, const char* path);
 int ppo_carla_pth_load(const ppo_carla_layout* L, const char* path, float* params, long n);
+/* the same for any ppo_carla_arch (ppo_carla.h: ppo_carla_layout2_fill and ppo_carla_tensor_name are
+ * exported from the same file): the module tree holds the LayerNorm children and the parameterless
+ * ReLUs at the reference's Sequential indices (carla_model.h:44-64, :113-175). Loading an archive
+ * written for another arch fails and names the first parameter it lacks. */
+int ppo_carla_pth_save2(const ppo_carla_layout2* L, const float* params, const char* path);
+int ppo_carla_pth_load2(const ppo_carla_layout2* L, const char* path, float* params, long n);
 
 #ifdef __cplusplus
 }

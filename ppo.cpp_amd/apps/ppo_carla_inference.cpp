@@ -10,7 +10,9 @@
 //   over the models (ppo_carla_inference.cpp:163-194).
 // Exit codes as the reference: 1 handshake failed, 2 no model file, 3 connection interrupted.
 // The agent is the repo's CaRL forward on the GPU (include/ppo_carla.h: implicit-GEMM MFMA
-// convolutions, Beta head); model files are read by the LibTorch-compatible reader (ppo_pth.h).
+// convolutions, Beta head; config.json's image_encoder "roach" | "roach_ln", use_layer_norm and
+// use_layer_norm_policy_head choose the architecture); model files are read by the
+// LibTorch-compatible reader (ppo_pth.h).
 // Sampling per model i uses the Philox contract with seed config.seed + i (the reference seeds a
 // CUDA generator with seed + i, ppo_carla_inference.cpp:118-126), step counter = query index.
 #include <hip/hip_runtime.h>
@@ -56,8 +58,20 @@ int main(int argc, const char** argv) {
   // config.json next to the models (carla_config.h update_from_json): the fields the agent needs
   const std::filesystem::path model_folder(path_to_conf_file);
   const FlatJson cfg = FlatJson::parse_file((model_folder / "config.json").string());
-  if (cfg.get_string("image_encoder", "roach") != "roach")
-    throw std::runtime_error("ppo_carla_inference: only the 'roach' image encoder is built (carla_model.h:65-127)");
+  // the architecture switches of carla_model.h:44-64 / :113-175 (defaults of carla_config.h)
+  const std::string encoder = cfg.get_string("image_encoder", "roach");
+  if (encoder == "roach_ln2")
+    throw std::runtime_error("ppo_carla_inference: the 'roach_ln2' image encoder (seven convolutions on a 256 x 256 "
+                             "bev, carla_model.h:80-103) is not built; 'roach' and 'roach_ln' are");
+  if (encoder != "roach" && encoder != "roach_ln")
+    throw std::runtime_error("Unsupported image_encoder chosen. Options roach, roach_ln. Chosen option: " + encoder);
+  if (cfg.get_bool("use_positional_encoding", false))
+    throw std::runtime_error(
+        "ppo_carla_inference: use_positional_encoding is not built (carla_model.h:39-42, :226-234)");
+  ppo_carla_arch arch;
+  arch.encoder_ln = encoder == "roach_ln" ? 1 : 0;
+  arch.mlp_ln = cfg.get_bool("use_layer_norm", false) ? 1 : 0;
+  arch.policy_ln = cfg.get_bool("use_layer_norm_policy_head", true) ? 1 : 0;
   ppo_carla_config cc;
   std::memset(&cc, 0, sizeof(cc));
   cc.obs_channels = cfg.get_int("obs_num_channels", 15);
@@ -91,17 +105,17 @@ int main(int argc, const char** argv) {
 
   HIPCHECK(hipSetDevice(0));
   std::vector<ppo_carla_t*> agents;
-  ppo_carla_layout L;
+  ppo_carla_layout2 L;
   for (const auto& entry : std::filesystem::recursive_directory_iterator(model_folder)) {
     const std::string fn = entry.path().filename().string();
     if (fn.rfind("model", 0) == 0 && fn.size() >= 4 && fn.compare(fn.size() - 4, 4, ".pth") == 0) {
       ppo_carla_config ci = cc;
       ci.seed = (uint64_t)(seed + (int)agents.size());
       ppo_carla_t* a = nullptr;
-      check(ppo_carla_create(&ci, 0, &a), "ppo_carla_create");
-      check(ppo_carla_get_layout(a, &L), "ppo_carla_get_layout");
+      check(ppo_carla_create2(&ci, &arch, 0, nullptr, &a), "ppo_carla_create2");
+      check(ppo_carla_get_layout2(a, &L), "ppo_carla_get_layout2");
       std::vector<float> p(L.P);
-      check(ppo_carla_pth_load(&L, entry.path().string().c_str(), p.data(), L.P), "torch::load of the model");
+      check(ppo_carla_pth_load2(&L, entry.path().string().c_str(), p.data(), L.P), "torch::load of the model");
       check(ppo_carla_load_params(a, p.data(), L.P), "ppo_carla_load_params");
       agents.push_back(a);
     }

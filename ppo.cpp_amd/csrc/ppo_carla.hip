@@ -1302,6 +1302,302 @@ int launch_conv(const ConvArgs& a, hipStream_t s, int img = 1, bool fin = true, 
   return 0;
 }
 
+// ==========================================================================================
+// LayerNorm + ReLU (carla_model.h:44-64 roach_ln, :113-175 use_layer_norm; nn::LayerNorm defaults:
+// biased variance, eps 1e-5, per-element weight / bias shared over rows). A normalised layer's
+// convolution / Linear runs with relu = 0 into a pre-activation buffer z and k_carla_ln writes
+// relu(x^ * gamma + beta) where the layer's output goes today, so the next layer and every gradient
+// kernel see what they see without LayerNorm. All kernels are memory-bound row or column sweeps;
+// every sum is a per-thread strided loop and an LDS tree: a fixed order, no atomics.
+// ==========================================================================================
+constexpr float kLnEps = 1e-5f;
+
+template <int T = 256>
+PPO_DEV float ln_block_sum(float v, float* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = T / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  const float r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// One row per workgroup: mean, then the variance about that mean (second sweep), then y (third).
+// VEC: 16-byte loads / stores of z and y (F and both strides multiples of 4, both bases 16-byte
+// aligned); gamma / beta sit at arbitrary float offsets of the parameter vector.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_carla_ln(const float* __restrict__ in, long in_stride, float* __restrict__ out,
+                                                  long out_stride, int F, const float* __restrict__ gamma,
+                                                  const float* __restrict__ beta, float* __restrict__ stat) {
+  __shared__ float red[256];
+  const long r = blockIdx.x;
+  const float* z = in + r * in_stride;
+  float* y = out + r * out_stride;
+  float s = 0.f;
+  if (VEC) {
+    const float4* z4 = reinterpret_cast<const float4*>(z);
+    for (int i = threadIdx.x; i < F / 4; i += 256) {
+      const float4 v = z4[i];
+      s += (v.x + v.y) + (v.z + v.w);
+    }
+  } else {
+    for (int i = threadIdx.x; i < F; i += 256) s += z[i];
+  }
+  const float mean0 = ln_block_sum(s, red) / (float)F;
+  // corrected two-pass (Chan, Golub, LeVeque): the second sweep also sums the residuals z - mean0,
+  // which carry the rounding error of the first sum; mean = mean0 + e, var = sum (z - mean0)^2 / F - e^2
+  float q = 0.f, e1 = 0.f;
+  if (VEC) {
+    const float4* z4 = reinterpret_cast<const float4*>(z);
+    for (int i = threadIdx.x; i < F / 4; i += 256) {
+      const float4 v = z4[i];
+      const float a = v.x - mean0, b = v.y - mean0, c = v.z - mean0, d = v.w - mean0;
+      q += (a * a + b * b) + (c * c + d * d);
+      e1 += (a + b) + (c + d);
+    }
+  } else {
+    for (int i = threadIdx.x; i < F; i += 256) {
+      const float a = z[i] - mean0;
+      q += a * a;
+      e1 += a;
+    }
+  }
+  const float e = ln_block_sum(e1, red) / (float)F;
+  const float mean = mean0 + e;
+  const float rstd = 1.0f / sqrtf(fmaxf(ln_block_sum(q, red) / (float)F - e * e, 0.f) + kLnEps);
+  if (threadIdx.x == 0) {
+    stat[2 * r] = mean;
+    stat[2 * r + 1] = rstd;
+  }
+  if (VEC) {
+    const float4* z4 = reinterpret_cast<const float4*>(z);
+    float4* y4 = reinterpret_cast<float4*>(y);
+    for (int i = threadIdx.x; i < F / 4; i += 256) {
+      const float4 v = z4[i];
+      const float* g = gamma + 4 * i;
+      const float* b = beta + 4 * i;
+      float4 o;
+      o.x = fmaxf((v.x - mean) * rstd * g[0] + b[0], 0.f);
+      o.y = fmaxf((v.y - mean) * rstd * g[1] + b[1], 0.f);
+      o.z = fmaxf((v.z - mean) * rstd * g[2] + b[2], 0.f);
+      o.w = fmaxf((v.w - mean) * rstd * g[3] + b[3], 0.f);
+      y4[i] = o;
+    }
+  } else {
+    for (int i = threadIdx.x; i < F; i += 256) y[i] = fmaxf((z[i] - mean) * rstd * gamma[i] + beta[i], 0.f);
+  }
+}
+
+// The same for long rows (F >= kLnBigMin, vector-aligned): at training batch sizes every row is in flight
+// at once (2 048 x 283 KB against 32 MB of L2), so k_carla_ln's second and third sweeps would come from
+// HBM again. Here a workgroup of 1 024 threads keeps its row in registers (NV float4 per thread, F <=
+// 4 096 NV): one read, one write. Same arithmetic per element; the sums take another (fixed) order.
+constexpr int kLnBigThreads = 1024, kLnBigMin = 4096, kLnBigMaxVec = 18;
+
+template <int NV>
+__global__ __launch_bounds__(kLnBigThreads) void k_carla_ln_big(const float* __restrict__ in, long in_stride,
+                                                                float* __restrict__ out, long out_stride, int F,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta,
+                                                                float* __restrict__ stat) {
+  __shared__ float red[kLnBigThreads];
+  const long r = blockIdx.x;
+  const float4* z4 = reinterpret_cast<const float4*>(in + r * in_stride);
+  float4* y4 = reinterpret_cast<float4*>(out + r * out_stride);
+  const int F4 = F / 4;
+  float4 v[NV];
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = k * kLnBigThreads + threadIdx.x;
+    v[k] = i < F4 ? z4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+  }
+  const float mean0 = ln_block_sum<kLnBigThreads>(s, red) / (float)F;
+  float q = 0.f, e1 = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    if (k * kLnBigThreads + (int)threadIdx.x < F4) {
+      const float a = v[k].x - mean0, b = v[k].y - mean0, c = v[k].z - mean0, d = v[k].w - mean0;
+      q += (a * a + b * b) + (c * c + d * d);
+      e1 += (a + b) + (c + d);
+    }
+  }
+  const float e = ln_block_sum<kLnBigThreads>(e1, red) / (float)F;
+  const float mean = mean0 + e;
+  const float rstd = 1.0f / sqrtf(fmaxf(ln_block_sum<kLnBigThreads>(q, red) / (float)F - e * e, 0.f) + kLnEps);
+  if (threadIdx.x == 0) {
+    stat[2 * r] = mean;
+    stat[2 * r + 1] = rstd;
+  }
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = k * kLnBigThreads + threadIdx.x;
+    if (i < F4) {
+      const float* g = gamma + 4 * i;
+      const float* b = beta + 4 * i;
+      float4 o;
+      o.x = fmaxf((v[k].x - mean) * rstd * g[0] + b[0], 0.f);
+      o.y = fmaxf((v[k].y - mean) * rstd * g[1] + b[1], 0.f);
+      o.z = fmaxf((v[k].z - mean) * rstd * g[2] + b[2], 0.f);
+      o.w = fmaxf((v[k].w - mean) * rstd * g[3] + b[3], 0.f);
+      y4[i] = o;
+    }
+  }
+}
+
+// Row pass of the backward, in place: d holds dy * [y > 0] on entry (the consuming layer's
+// input-gradient kernel applied the mask) and dz = rstd * (g - a - x^ * b) on exit, with g = d * gamma,
+// a = sum g / F, b = sum g x^ / F. Each thread rewrites only the elements it read in the second sweep.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_carla_ln_bwd(float* __restrict__ d, long d_stride,
+                                                      const float* __restrict__ zin, long z_stride, int F,
+                                                      const float* __restrict__ gamma,
+                                                      const float* __restrict__ stat) {
+  __shared__ float red[256];
+  const long r = blockIdx.x;
+  float* dr = d + r * d_stride;
+  const float* z = zin + r * z_stride;
+  const float mean = stat[2 * r], rstd = stat[2 * r + 1];
+  float sa = 0.f, sb = 0.f;
+  if (VEC) {
+    const float4* z4 = reinterpret_cast<const float4*>(z);
+    const float4* d4 = reinterpret_cast<const float4*>(dr);
+    for (int i = threadIdx.x; i < F / 4; i += 256) {
+      const float4 v = z4[i], dv = d4[i];
+      const float* g = gamma + 4 * i;
+      const float g0 = dv.x * g[0], g1 = dv.y * g[1], g2 = dv.z * g[2], g3 = dv.w * g[3];
+      sa += (g0 + g1) + (g2 + g3);
+      sb += (g0 * ((v.x - mean) * rstd) + g1 * ((v.y - mean) * rstd)) +
+            (g2 * ((v.z - mean) * rstd) + g3 * ((v.w - mean) * rstd));
+    }
+  } else {
+    for (int i = threadIdx.x; i < F; i += 256) {
+      const float g = dr[i] * gamma[i];
+      sa += g;
+      sb += g * ((z[i] - mean) * rstd);
+    }
+  }
+  const float a = ln_block_sum(sa, red) / (float)F;
+  const float b = ln_block_sum(sb, red) / (float)F;
+  if (VEC) {
+    const float4* z4 = reinterpret_cast<const float4*>(z);
+    float4* d4 = reinterpret_cast<float4*>(dr);
+    for (int i = threadIdx.x; i < F / 4; i += 256) {
+      const float4 v = z4[i], dv = d4[i];
+      const float* g = gamma + 4 * i;
+      float4 o;
+      o.x = rstd * (dv.x * g[0] - a - (v.x - mean) * rstd * b);
+      o.y = rstd * (dv.y * g[1] - a - (v.y - mean) * rstd * b);
+      o.z = rstd * (dv.z * g[2] - a - (v.z - mean) * rstd * b);
+      o.w = rstd * (dv.w * g[3] - a - (v.w - mean) * rstd * b);
+      d4[i] = o;
+    }
+  } else {
+    for (int i = threadIdx.x; i < F; i += 256) dr[i] = rstd * (dr[i] * gamma[i] - a - (z[i] - mean) * rstd * b);
+  }
+}
+
+// Column pass: dgamma[e] = sum over rows d * x^, dbeta[e] = sum over rows d (d = dy * [y > 0], so this
+// runs before the in-place row pass). blockIdx.y = a chunk of rpc consecutive rows, a thread = one
+// element (coalesced over e); part [chunks][2][F]. k_carla_ln_dgb_sum adds the chunks in order, as
+// k_wsum does for the weight gradients.
+__global__ __launch_bounds__(256) void k_carla_ln_dgb(const float* __restrict__ d, long d_stride,
+                                                      const float* __restrict__ z, long z_stride, int n, int F,
+                                                      int rpc, const float* __restrict__ stat,
+                                                      float* __restrict__ part) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= F) return;
+  const int r0 = blockIdx.y * rpc, r1 = r0 + rpc < n ? r0 + rpc : n;
+  float dg = 0.f, db = 0.f;
+  for (int r = r0; r < r1; ++r) {
+    const float dv = d[(long)r * d_stride + e];
+    dg += dv * ((z[(long)r * z_stride + e] - stat[2 * r]) * stat[2 * r + 1]);
+    db += dv;
+  }
+  part[((long)blockIdx.y * 2) * F + e] = dg;
+  part[((long)blockIdx.y * 2 + 1) * F + e] = db;
+}
+
+__global__ __launch_bounds__(256) void k_carla_ln_dgb_sum(const float* __restrict__ part, int chunks, int F,
+                                                          float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= F) return;
+  float dg = 0.f, db = 0.f;
+  for (int c = 0; c < chunks; ++c) {
+    dg += part[((long)c * 2) * F + e];
+    db += part[((long)c * 2 + 1) * F + e];
+  }
+  dgamma[e] = dg;
+  dbeta[e] = db;
+}
+
+// (hook only) what the consuming layer's input-gradient kernel does in the agent: d = dy * [y > 0]
+__global__ void k_carla_ln_mask(const float* __restrict__ dy, const float* __restrict__ y, long y_stride, int n, int F,
+                                float* __restrict__ d) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)n * F) return;
+  const long r = i / F;
+  d[i] = y[r * y_stride + (i - r * F)] > 0.0f ? dy[i] : 0.0f;
+}
+
+// column-pass chunks aimed at for n rows: about 1024 workgroups over (column blocks x chunks), at most
+// 64 and at most n. Non-decreasing in n.
+int ln_max_chunks(int n, int F) {
+  const int cb = (F + 255) / 256;
+  return std::max(1, std::min((1024 + cb - 1) / cb, std::min(n, 64)));
+}
+int ln_rows_per_chunk(int n, int F) {
+  const int chunks = ln_max_chunks(n, F);
+  return (n + chunks - 1) / chunks;
+}
+// Partial-sum floats that serve every batch of up to max_n rows. The chunks a batch of n rows really
+// uses, ceil(n / rows per chunk), are at most ln_max_chunks(n) <= ln_max_chunks(max_n), but not
+// monotone in n, so the buffer is sized by that bound and not by max_n's own chunk count.
+size_t ln_part_floats(int max_n, int F) { return (size_t)ln_max_chunks(max_n, F) * 2 * F; }
+
+bool ln_vec_ok(const void* a, long as, const void* b, long bs, int F) {
+  return F % 4 == 0 && as % 4 == 0 && bs % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 &&
+         (reinterpret_cast<uintptr_t>(b) & 15) == 0;
+}
+
+void launch_ln_fwd(int n, int F, const float* z, long zs, const float* gamma, const float* beta, float* y, long ys,
+                   float* stat, hipStream_t s) {
+  const bool vec = ln_vec_ok(z, zs, y, ys, F);
+  const int nv = (F / 4 + kLnBigThreads - 1) / kLnBigThreads;
+#define PPO_LN_BIG(NV_) \
+  hipLaunchKernelGGL((k_carla_ln_big<NV_>), dim3(n), dim3(kLnBigThreads), 0, s, z, zs, y, ys, F, gamma, beta, stat)
+  if (vec && F >= kLnBigMin && nv <= kLnBigMaxVec) {
+    if (nv <= 2) PPO_LN_BIG(2);
+    else if (nv <= 4) PPO_LN_BIG(4);
+    else if (nv <= 8) PPO_LN_BIG(8);
+    else PPO_LN_BIG(kLnBigMaxVec);
+  } else if (vec) {
+    hipLaunchKernelGGL((k_carla_ln<true>), dim3(n), dim3(256), 0, s, z, zs, y, ys, F, gamma, beta, stat);
+  } else {
+    hipLaunchKernelGGL((k_carla_ln<false>), dim3(n), dim3(256), 0, s, z, zs, y, ys, F, gamma, beta, stat);
+  }
+#undef PPO_LN_BIG
+}
+
+// d [n][F] (stride ds): dy * [y > 0] in, dz out; part holds part_cap floats (ln_part_floats of the largest
+// batch). Returns -1, launching nothing, if this batch's chunks would not fit.
+int launch_ln_bwd(int n, int F, float* d, long ds, const float* z, long zs, const float* gamma, const float* stat,
+                  float* dgamma, float* dbeta, float* part, size_t part_cap, hipStream_t s) {
+  const int rpc = ln_rows_per_chunk(n, F), chunks = (n + rpc - 1) / rpc, cb = (F + 255) / 256;
+  if ((size_t)chunks * 2 * F > part_cap) return -1;
+  hipLaunchKernelGGL(k_carla_ln_dgb, dim3(cb, chunks), dim3(256), 0, s, d, ds, z, zs, n, F, rpc, stat, part);
+  hipLaunchKernelGGL(k_carla_ln_dgb_sum, dim3(cb), dim3(256), 0, s, part, chunks, F, dgamma, dbeta);
+  if (ln_vec_ok(d, ds, z, zs, F))
+    hipLaunchKernelGGL((k_carla_ln_bwd<true>), dim3(n), dim3(256), 0, s, d, ds, z, zs, F, gamma, stat);
+  else
+    hipLaunchKernelGGL((k_carla_ln_bwd<false>), dim3(n), dim3(256), 0, s, d, ds, z, zs, F, gamma, stat);
+  return 0;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -1309,7 +1605,7 @@ int launch_conv(const ConvArgs& a, hipStream_t s, int img = 1, bool fin = true, 
 // ------------------------------------------------------------------------------------------
 struct ppo_carla {
   ppo_carla_config cfg;
-  ppo_carla_layout L;
+  ppo_carla_layout2 L;  // arch all zero: the offsets of ppo_carla_layout
   int device = 0;
   hipStream_t stream = nullptr;
   float* P = nullptr;
@@ -1359,6 +1655,19 @@ struct ppo_carla {
   // data parallelism (ppo_carla_comm_init): one RCCL communicator, any world >= 1
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
+  // LayerNorm agents (ppo_carla_create2): per normalised layer the pre-activation z [B][F] and the
+  // row statistics {mean, rstd} [B][2]; ln[k].F == 0: the layer has no LayerNorm. lnpart: the column
+  // pass's chunk sums (carla_train_init).
+  struct Ln {
+    int F = 0;
+    long g = -1, be = -1;
+    float *z = nullptr, *stat = nullptr;
+  };
+  enum { kLnConv = 0, kLnS1 = 6, kLnS2, kLnL1, kLnFeat, kLnV1, kLnV2, kLnP1, kLnP2, kLnCount };
+  Ln ln[kLnCount];
+  bool any_ln = false;
+  float* lnpart = nullptr;
+  size_t lnpart_floats = 0;
 };
 
 static int carla_alloc(float** p, size_t n) {
@@ -1381,6 +1690,11 @@ extern "C" int ppo_carla_destroy(ppo_carla_t* c) {
     if (b) (void)hipFree(b);
   for (float* b : c->dact)
     if (b) (void)hipFree(b);
+  for (auto& l : c->ln) {
+    if (l.z) (void)hipFree(l.z);
+    if (l.stat) (void)hipFree(l.stat);
+  }
+  if (c->lnpart) (void)hipFree(c->lnpart);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;
@@ -1391,9 +1705,15 @@ extern "C" int ppo_carla_create(const ppo_carla_config* cfg, int device, ppo_car
 }
 
 extern "C" int ppo_carla_create_ex(const ppo_carla_config* cfg, int device, const char* options, ppo_carla_t** out) {
+  return ppo_carla_create2(cfg, nullptr, device, options, out);
+}
+
+extern "C" int ppo_carla_create2(const ppo_carla_config* cfg, const ppo_carla_arch* arch, int device,
+                                 const char* options, ppo_carla_t** out) {
   if (!cfg || !out) return ppo_fail("ppo_carla_create: null argument", -1);
   int conv_img = kConv1Auto;
   int tail_mode = 1;
+  const char* tail_given = nullptr;
   int c1bx = kConv1BxAuto;
   int dgrad_q = kDgradQuadAuto;
   int wgrad_t = kWgradTiledAuto;
@@ -1409,8 +1729,8 @@ extern "C" int ppo_carla_create_ex(const ppo_carla_config* cfg, int device, cons
       if (o == "conv1=packed") conv_img = 2;
       else if (o == "conv1=staged") conv_img = 1;
       else if (o == "conv1=generic") conv_img = 0;
-      else if (o == "tail=fused") tail_mode = 0;
-      else if (o == "tail=staged") tail_mode = 1;
+      else if (o == "tail=fused") tail_mode = 0, tail_given = "tail=fused";
+      else if (o == "tail=staged") tail_mode = 1, tail_given = "tail=staged";
       else if (o == "tail=layers") tail_mode = 2;
       else if (o == "conv1_mfma=bx3") c1bx = 1;
       else if (o == "conv1_mfma=f32") c1bx = 0;
@@ -1433,10 +1753,21 @@ extern "C" int ppo_carla_create_ex(const ppo_carla_config* cfg, int device, cons
       else return ppo_fail("ppo_carla_create_ex: unknown option " + o, -1);
     }
   }
+  // LayerNorm variants: refusals that need no device
+  const bool any_ln = arch && (arch->encoder_ln || arch->mlp_ln);
+  if (arch && (arch->encoder_ln < 0 || arch->encoder_ln > 1))
+    return ppo_fail("ppo_carla_create2: encoder_ln must be 0 (roach) or 1 (roach_ln); roach_ln2 is not built", -1);
+  if (arch && arch->encoder_ln && (cfg->bev_h != 192 || cfg->bev_w != 192))
+    return ppo_fail("ppo_carla_create2: the roach_ln encoder needs a 192 x 192 bev: the reference hard-codes its "
+                    "LayerNorm shapes ([8, 94, 94] ... [256, 2, 2], carla_model.h:45-62)", -1);
+  if (any_ln && tail_given)
+    return ppo_fail(std::string("ppo_carla_create2: option ") + tail_given +
+                    " cannot be used by a LayerNorm agent (its forward runs one launch per layer, tail=layers)", -1);
+  if (any_ln) tail_mode = 2;
   if (int rc = ppo_runtime_check()) return rc;
-  ppo_carla_layout L;
-  if (ppo_carla_layout_init(&L, cfg->obs_channels, cfg->bev_h, cfg->bev_w, cfg->num_measurements,
-                            cfg->num_value_measurements, cfg->action_dim) != 0)
+  ppo_carla_layout2 L{};  // unused table entries stay zero
+  if (ppo_carla_layout2_init(&L, cfg->obs_channels, cfg->bev_h, cfg->bev_w, cfg->num_measurements,
+                             cfg->num_value_measurements, cfg->action_dim, arch) != 0)
     return ppo_fail("ppo_carla_create: the roach encoder needs a bev that ends at 256 x 2 x 2 (n_flatten = 1024, "
                     "carla_model.h:110)", -1);
   if (cfg->max_batch <= 0) return ppo_fail("ppo_carla_create: max_batch must be positive", -1);
@@ -1487,6 +1818,27 @@ extern "C" int ppo_carla_create_ex(const ppo_carla_config* cfg, int device, cons
   }
   rc |= carla_alloc(&c->c1w, (size_t)img3_blocks(L.C, L.conv_k[0]) * 256);
   rc |= carla_alloc(reinterpret_cast<float**>(&c->tail_bar), 1);
+  {  // pre-activation and statistics buffers of the normalised layers
+    auto ln = [&](int k, int F, long g, long be) {
+      if (g < 0) return;
+      c->ln[k].F = F;
+      c->ln[k].g = g;
+      c->ln[k].be = be;
+      rc |= carla_alloc(&c->ln[k].z, B * F);
+      rc |= carla_alloc(&c->ln[k].stat, B * 2);
+      c->any_ln = true;
+    };
+    for (int i = 0; i < PPO_CARLA_NCONV; ++i)
+      ln(ppo_carla::kLnConv + i, L.conv_oc[i] * L.conv_oh[i] * L.conv_ow[i], L.conv_g[i], L.conv_be[i]);
+    ln(ppo_carla::kLnS1, 256, L.st_g[0], L.st_be[0]);
+    ln(ppo_carla::kLnS2, 256, L.st_g[1], L.st_be[1]);
+    ln(ppo_carla::kLnL1, 512, L.lin_g[0], L.lin_be[0]);
+    ln(ppo_carla::kLnFeat, 256, L.lin_g[1], L.lin_be[1]);
+    ln(ppo_carla::kLnV1, 256, L.v_g[0], L.v_be[0]);
+    ln(ppo_carla::kLnV2, 256, L.v_g[1], L.v_be[1]);
+    ln(ppo_carla::kLnP1, 256, L.pi_g[0], L.pi_be[0]);
+    ln(ppo_carla::kLnP2, 256, L.pi_g[1], L.pi_be[1]);
+  }
   if (rc || hipDeviceSynchronize() != hipSuccess) {
     ppo_carla_destroy(c);
     return ppo_fail("ppo_carla_create: device allocation failed", -2);
@@ -1495,8 +1847,30 @@ extern "C" int ppo_carla_create_ex(const ppo_carla_config* cfg, int device, cons
   return 0;
 }
 
+static_assert(offsetof(ppo_carla_layout, sg_b) == offsetof(ppo_carla_layout2, sg_b) &&
+                  offsetof(ppo_carla_layout, ntensors) == offsetof(ppo_carla_layout, sg_b) + sizeof(long),
+              "ppo_carla_layout2 must begin with ppo_carla_layout's fields");
+
 extern "C" int ppo_carla_get_layout(const ppo_carla_t* c, ppo_carla_layout* out) {
   if (!c || !out) return ppo_fail("ppo_carla_get_layout: null argument", -1);
+  if (c->any_ln)
+    return ppo_fail("ppo_carla_get_layout: ppo_carla_layout cannot describe a LayerNorm agent's tensors; use "
+                    "ppo_carla_get_layout2", -1);
+  // the default arch's layout2 holds ppo_carla_layout's fields with the same values, in the same order
+  // up to the tensor table
+  const ppo_carla_layout2& L = c->L;
+  memcpy(out, &L, offsetof(ppo_carla_layout, ntensors));
+  out->ntensors = L.ntensors;
+  for (int t = 0; t < PPO_CARLA_MAX_TENSORS; ++t) {
+    out->t_off[t] = L.t_off[t];
+    out->t_len[t] = L.t_len[t];
+    out->t_grad[t] = L.t_grad[t];
+  }
+  return 0;
+}
+
+extern "C" int ppo_carla_get_layout2(const ppo_carla_t* c, ppo_carla_layout2* out) {
+  if (!c || !out) return ppo_fail("ppo_carla_get_layout2: null argument", -1);
   *out = c->L;
   return 0;
 }
@@ -1521,7 +1895,7 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
   if (sample_type < PPO_CARLA_SAMPLE || sample_type > PPO_CARLA_ROACH)
     return ppo_fail("Unsupported sample type used. Sample type: " + std::to_string(sample_type), -1);
   if (sample_type == PPO_CARLA_GIVEN && !action_in) return ppo_fail("ppo_carla_forward: GIVEN needs action_in", -1);
-  const ppo_carla_layout& L = c->L;
+  const ppo_carla_layout2& L = c->L;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const float* P = c->P;
   auto conv = [&](const float* in_f, const uint8_t* in_u8, long in_stride, int IC, int IH, int IW, long w, long b,
@@ -1535,6 +1909,18 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
   };
   auto linear = [&](const float* in, long in_stride, int IN, long w, long b, float* out, long out_stride, int OUT,
                     int relu) { return conv(in, nullptr, in_stride, IN, 1, 1, w, b, out, out_stride, OUT, 1, 1, 1, 1, relu); };
+  // a normalised layer: the pre-activation goes to ln[k].z, k_carla_ln writes the layer's output
+  auto norm = [&](int k, float* out, long out_stride) {
+    const ppo_carla::Ln& l = c->ln[k];
+    launch_ln_fwd(n, l.F, l.z, l.F, P + l.g, P + l.be, out, out_stride, l.stat, s);
+  };
+  auto linear_act = [&](int k, const float* in, long in_stride, int IN, long w, long b, float* out, long out_stride,
+                        int OUT) {
+    if (!c->ln[k].F) return linear(in, in_stride, IN, w, b, out, out_stride, OUT, 1);
+    const int r = linear(in, in_stride, IN, w, b, c->ln[k].z, OUT, OUT, 0);
+    norm(k, out, out_stride);
+    return r;
+  };
   int rc = 0;
   const bool fused_tail = c->tail_mode != 2 && n <= kTailMaxN;
   ConvArgs c6{};
@@ -1553,6 +1939,11 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
                     P + L.conv_b[i], out, out_stride, L.conv_oc[i], L.conv_oh[i], L.conv_ow[i], L.conv_k[i],
                     L.conv_s[i], 1, n, c->ksplit, 0};
       rc |= launch_conv(c6, s, c->conv_img, false, &c6_Z);
+    } else if (c->ln[ppo_carla::kLnConv + i].F) {  // roach_ln: conv -> LayerNorm([OC, OH, OW]) -> ReLU
+      const ppo_carla::Ln& l = c->ln[ppo_carla::kLnConv + i];
+      rc |= conv(cur, img, cur_stride, L.conv_ic[i], L.conv_ih[i], L.conv_iw[i], L.conv_w[i], L.conv_b[i], l.z, l.F,
+                 L.conv_oc[i], L.conv_oh[i], L.conv_ow[i], L.conv_k[i], L.conv_s[i], 0);
+      norm(ppo_carla::kLnConv + i, out, out_stride);
     } else {
       rc |= conv(cur, img, cur_stride, L.conv_ic[i], L.conv_ih[i], L.conv_iw[i], L.conv_w[i], L.conv_b[i], out,
                  out_stride, L.conv_oc[i], L.conv_oh[i], L.conv_ow[i], L.conv_k[i], L.conv_s[i], 1);
@@ -1619,18 +2010,18 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
     return 0;
   }
   // state_linear (:238) -> columns 1024..1279; linear (:240) -> features = value-head input columns 0..255
-  rc |= linear(meas, L.NM, L.NM, L.st_w[0], L.st_b[0], c->s1, 256, 256, 1);
-  rc |= linear(c->s1, 256, 256, L.st_w[1], L.st_b[1], c->enc + 1024, 1280, 256, 1);
-  rc |= linear(c->enc, 1280, 1280, L.lin_w[0], L.lin_b[0], c->l1, 512, 512, 1);
-  rc |= linear(c->l1, 512, 512, L.lin_w[1], L.lin_b[1], c->feat, FW, 256, 1);
+  rc |= linear_act(ppo_carla::kLnS1, meas, L.NM, L.NM, L.st_w[0], L.st_b[0], c->s1, 256, 256);
+  rc |= linear_act(ppo_carla::kLnS2, c->s1, 256, 256, L.st_w[1], L.st_b[1], c->enc + 1024, 1280, 256);
+  rc |= linear_act(ppo_carla::kLnL1, c->enc, 1280, 1280, L.lin_w[0], L.lin_b[0], c->l1, 512, 512);
+  rc |= linear_act(ppo_carla::kLnFeat, c->l1, 512, 512, L.lin_w[1], L.lin_b[1], c->feat, FW, 256);
   if (L.NV > 0)
     hipLaunchKernelGGL(k_carla_pack, dim3((n * L.NV + 255) / 256), dim3(256), 0, s, vmeas, c->feat, n, L.NV);
   // value_head on [features | value_measurements] (:276-277), policy_head on features (:279)
-  rc |= linear(c->feat, FW, (int)FW, L.v_w[0], L.v_b[0], c->v1, 256, 256, 1);
-  rc |= linear(c->v1, 256, 256, L.v_w[1], L.v_b[1], c->v2, 256, 256, 1);
+  rc |= linear_act(ppo_carla::kLnV1, c->feat, FW, (int)FW, L.v_w[0], L.v_b[0], c->v1, 256, 256);
+  rc |= linear_act(ppo_carla::kLnV2, c->v1, 256, 256, L.v_w[1], L.v_b[1], c->v2, 256, 256);
   rc |= linear(c->v2, 256, 256, L.v_w[2], L.v_b[2], c->val, 1, 1, 0);
-  rc |= linear(c->feat, FW, 256, L.pi_w[0], L.pi_b[0], c->p1, 256, 256, 1);
-  rc |= linear(c->p1, 256, 256, L.pi_w[1], L.pi_b[1], c->p2, 256, 256, 1);
+  rc |= linear_act(ppo_carla::kLnP1, c->feat, FW, 256, L.pi_w[0], L.pi_b[0], c->p1, 256, 256);
+  rc |= linear_act(ppo_carla::kLnP2, c->p1, 256, 256, L.pi_w[1], L.pi_b[1], c->p2, 256, 256);
   if (rc) return ppo_fail("ppo_carla_forward: no convolution kernel for this shape", -1);
   HeadArgs h{P,          L.mu_w, L.mu_b,   L.sg_w,    L.sg_b,    L.hi,    L.lo,
              c->p2,      c->val, n,        L.A,       sample_type, c->cfg.beta_min, action_in,
@@ -3313,7 +3704,7 @@ static int launch_wgrad_generic(WgradArgs a, float* Gw, float* Gb, float* part, 
 }  // namespace
 
 // the largest wgrad partial buffer any layer needs at max_batch rows
-static size_t carla_part_floats(const ppo_carla_layout& L, long B) {
+static size_t carla_part_floats(const ppo_carla_layout2& L, long B) {
   size_t m = 0;
   auto need = [&](int OC, int Kt, long Q) {
     const size_t f = plan_wgrad(OC, Kt, Q).part_floats;
@@ -3331,9 +3722,12 @@ static size_t carla_part_floats(const ppo_carla_layout& L, long B) {
   return m;
 }
 
+// c->small: where the per-tensor norm slices start (after the int64 tensor table at float 128)
+constexpr int kSmallNorm = 128 + 4 * PPO_CARLA_MAX_TENSORS2;
+
 static int carla_train_init(ppo_carla_t* c) {
   if (c->train_ready) return 0;
-  const ppo_carla_layout& L = c->L;
+  const ppo_carla_layout2& L = c->L;
   const size_t B = (size_t)c->cfg.max_batch;
   int rc = 0;
   rc |= carla_alloc(&c->G, L.P);
@@ -3367,14 +3761,21 @@ static int carla_train_init(ppo_carla_t* c) {
   rc |= carla_alloc(&c->dcol, dcol_f);
   rc |= carla_alloc(&c->wt, wt_f);
   rc |= carla_alloc(&c->zbias, zb_f);
-  // [0,2) adv mean/std, [64,71) stats + {total, coef}, [128,288) int64 tensor table, [320,...) norm slices
-  rc |= carla_alloc(&c->small, 320 + PPO_CARLA_MAX_TENSORS * kNormSplit);
+  if (c->any_ln) {
+    size_t f = 1;
+    for (const auto& l : c->ln)
+      if (l.F) f = std::max(f, ln_part_floats((int)B, l.F));
+    c->lnpart_floats = f;
+    rc |= carla_alloc(&c->lnpart, f);
+  }
+  // [0,2) adv mean/std, [64,71) stats + {total, coef}, [128,384) int64 tensor table, [384,...) norm slices
+  rc |= carla_alloc(&c->small, kSmallNorm + PPO_CARLA_MAX_TENSORS2 * kNormSplit);
   if (rc) return ppo_fail("ppo_carla_update: device allocation failed", -2);
   // tensor table (offsets / lengths as int64) after the scalars
-  std::vector<long> tab(2 * PPO_CARLA_MAX_TENSORS, 0);
+  std::vector<long> tab(2 * PPO_CARLA_MAX_TENSORS2, 0);
   for (int t = 0; t < L.ntensors; ++t) {
     tab[t] = L.t_off[t];
-    tab[PPO_CARLA_MAX_TENSORS + t] = L.t_grad[t] ? L.t_len[t] : 0;
+    tab[PPO_CARLA_MAX_TENSORS2 + t] = L.t_grad[t] ? L.t_len[t] : 0;
   }
   if (hipMemcpy(c->small + 128, tab.data(), tab.size() * sizeof(long), hipMemcpyHostToDevice) != hipSuccess)
     return ppo_fail("ppo_carla_update: copy failed", -2);
@@ -3393,7 +3794,7 @@ extern "C" int ppo_carla_update(ppo_carla_t* c, const ppo_carla_train_config* tc
   if (hipSetDevice(c->device) != hipSuccess) return ppo_fail("ppo_carla_update: hipSetDevice failed", -2);
   int rc = carla_train_init(c);
   if (rc) return rc;
-  const ppo_carla_layout& L = c->L;
+  const ppo_carla_layout2& L = c->L;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   // forward with the given actions (ac_ppo_carla.cpp:543-546); activations stay in the context
   rc = ppo_carla_forward(c, n, bev, meas, vmeas, PPO_CARLA_GIVEN, actions, 0, 0, nullptr, c->lp, c->ent, nullptr,
@@ -3430,6 +3831,14 @@ extern "C" int ppo_carla_update(ppo_carla_t* c, const ppo_carla_train_config* tc
     DgradArgs a{dz, dzs, P + w, w_in, x, xs, dx, dxs, IN, 1, 1, OUT, 1, 1, 1, 1, n, accumulate};
     bad |= launch_dgrad(a, s);
   };
+  // a normalised layer's backward, in place on its output gradient d (= dy * [y > 0] from the consuming
+  // layers' lin_d / dgrad): dgamma / dbeta, then d = dz, which the layer's own wgrad / dgrad read
+  auto ln_b = [&](int k, float* d, long ds) {
+    const ppo_carla::Ln& l = c->ln[k];
+    if (l.F)
+      bad |= launch_ln_bwd(n, l.F, d, ds, l.z, l.F, P + l.g, l.stat, G + l.g, G + l.be, c->lnpart, c->lnpart_floats,
+                           s);
+  };
   const long FW = 256 + L.NV;
   const int A = L.A;
   // heads (carla_model.h:279-284): dist_mu / dist_sigma on the policy latent
@@ -3438,29 +3847,38 @@ extern "C" int ppo_carla_update(ppo_carla_t* c, const ppo_carla_train_config* tc
   lin_d(c->dhead, 2 * A, A, L.mu_w, 256, c->p2, 256, c->dp2, 256, 256, 0);
   lin_d(c->dhead + A, 2 * A, A, L.sg_w, 256, c->p2, 256, c->dp2, 256, 256, 1);
   // policy_head (:279)
+  ln_b(ppo_carla::kLnP2, c->dp2, 256);
   lin_w(c->dp2, 256, 256, c->p1, 256, 256, L.pi_w[1], L.pi_b[1]);
   lin_d(c->dp2, 256, 256, L.pi_w[1], 256, c->p1, 256, c->dp1, 256, 256, 0);
+  ln_b(ppo_carla::kLnP1, c->dp1, 256);
   lin_w(c->dp1, 256, 256, c->feat, FW, 256, L.pi_w[0], L.pi_b[0]);
   lin_d(c->dp1, 256, 256, L.pi_w[0], 256, c->feat, FW, c->dfeat, 256, 256, 0);
   // value_head (:276-277)
   lin_w(c->dval, 1, 1, c->v2, 256, 256, L.v_w[2], L.v_b[2]);
   lin_d(c->dval, 1, 1, L.v_w[2], 256, c->v2, 256, c->dv2, 256, 256, 0);
+  ln_b(ppo_carla::kLnV2, c->dv2, 256);
   lin_w(c->dv2, 256, 256, c->v1, 256, 256, L.v_w[1], L.v_b[1]);
   lin_d(c->dv2, 256, 256, L.v_w[1], 256, c->v1, 256, c->dv1, 256, 256, 0);
+  ln_b(ppo_carla::kLnV1, c->dv1, 256);
   lin_w(c->dv1, 256, 256, c->feat, FW, (int)FW, L.v_w[0], L.v_b[0]);
   lin_d(c->dv1, 256, 256, L.v_w[0], (int)FW, c->feat, FW, c->dfeat, 256, 256, 1);
   // linear (:240) and state_linear (:238)
+  ln_b(ppo_carla::kLnFeat, c->dfeat, 256);
   lin_w(c->dfeat, 256, 256, c->l1, 512, 512, L.lin_w[1], L.lin_b[1]);
   lin_d(c->dfeat, 256, 256, L.lin_w[1], 512, c->l1, 512, c->dl1, 512, 512, 0);
+  ln_b(ppo_carla::kLnL1, c->dl1, 512);
   lin_w(c->dl1, 512, 512, c->enc, 1280, 1280, L.lin_w[0], L.lin_b[0]);
   lin_d(c->dl1, 512, 512, L.lin_w[0], 1280, c->enc, 1280, c->denc, 1280, 1280, 0);
+  ln_b(ppo_carla::kLnS2, c->denc + 1024, 1280);
   lin_w(c->denc + 1024, 1280, 256, c->s1, 256, 256, L.st_w[1], L.st_b[1]);
   lin_d(c->denc + 1024, 1280, 256, L.st_w[1], 256, c->s1, 256, c->ds1, 256, 256, 0);
+  ln_b(ppo_carla::kLnS1, c->ds1, 256);
   lin_w(c->ds1, 256, 256, meas, L.NM, L.NM, L.st_w[0], L.st_b[0]);
   // cnn (:236), last layer first; conv i reads act[i-1] (the image for i = 0)
   for (int i = PPO_CARLA_NCONV - 1; i >= 0; --i) {
-    const float* dz = i == PPO_CARLA_NCONV - 1 ? c->denc : c->dact[i];
+    float* dz = i == PPO_CARLA_NCONV - 1 ? c->denc : c->dact[i];
     const long dzs = i == PPO_CARLA_NCONV - 1 ? 1280 : (long)L.conv_oc[i] * L.conv_oh[i] * L.conv_ow[i];
+    ln_b(ppo_carla::kLnConv + i, dz, dzs);
     const float* xf = i > 0 ? c->act[i - 1] : nullptr;
     const long xs = (long)L.conv_ic[i] * L.conv_ih[i] * L.conv_iw[i];
     WgradArgs wa{dz,          dzs,         L.conv_oc[i], L.conv_oh[i] * L.conv_ow[i], L.conv_ow[i], xf,
@@ -3500,8 +3918,8 @@ extern "C" int ppo_carla_update(ppo_carla_t* c, const ppo_carla_train_config* tc
   // clip_grad_norm_ + Adam (ac_ppo_carla.cpp:618-619)
   const long* toff = (const long*)(sm + 128);
   hipLaunchKernelGGL(k_carla_tnorm, dim3(L.ntensors, kNormSplit), dim3(256), 0, s, G, toff,
-                     toff + PPO_CARLA_MAX_TENSORS, sm + 320);
-  hipLaunchKernelGGL(k_carla_tsum, dim3(1), dim3(64), 0, s, sm + 320, L.ntensors, tc->max_grad_norm, sm + 70);
+                     toff + PPO_CARLA_MAX_TENSORS2, sm + kSmallNorm);
+  hipLaunchKernelGGL(k_carla_tsum, dim3(1), dim3(64), 0, s, sm + kSmallNorm, L.ntensors, tc->max_grad_norm, sm + 70);
   c->step += 1;
   const double bc1 = 1.0 - std::pow(0.9, (double)c->step), bc2 = 1.0 - std::pow(0.999, (double)c->step);
   CarlaAdamArgs ad{P, G, c->m, c->v, begin, L.P - begin, sm + 70, (float)((double)lr / bc1), (float)std::sqrt(bc2),
@@ -3604,4 +4022,41 @@ extern "C" int ppo_carla_comm_broadcast_params(ppo_carla_t* c, int root) {
   if (ncclBroadcast(c->P, c->P, (size_t)c->L.P, ncclFloat, root, c->comm, c->stream) != ncclSuccess)
     return ppo_fail("ppo_carla_comm_broadcast_params: ncclBroadcast failed", -3);
   return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : ppo_fail("ppo_carla_comm_broadcast_params: sync failed", -2);
+}
+
+// ------------------------------------------------------------------------------------------
+// test hooks: the agent's LayerNorm launches on caller arrays (ppo_carla.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ppo_carla_debug_ln_forward(int n, int F, const float* z, long in_stride, const float* gamma,
+                                          const float* beta, float* y, long out_stride, float* stat, void* stream) {
+  if (!z || !gamma || !beta || !y || !stat) return ppo_fail("ppo_carla_debug_ln_forward: null argument", -1);
+  if (n <= 0 || F <= 0 || in_stride < F || out_stride < F)
+    return ppo_fail("ppo_carla_debug_ln_forward: n and F must be positive, strides at least F", -1);
+  if (int rc = ppo_runtime_check()) return rc;
+  launch_ln_fwd(n, F, z, in_stride, gamma, beta, y, out_stride, stat, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+    return ppo_fail("ppo_carla_debug_ln_forward: launch failed", -2);
+  return 0;
+}
+
+extern "C" int ppo_carla_debug_ln_backward(int n, int F, const float* z, long in_stride, const float* gamma,
+                                           const float* stat, const float* y, long out_stride, const float* dy,
+                                           float* dz, float* dgamma, float* dbeta, void* stream) {
+  if (!z || !gamma || !stat || !y || !dy || !dz || !dgamma || !dbeta)
+    return ppo_fail("ppo_carla_debug_ln_backward: null argument", -1);
+  if (n <= 0 || F <= 0 || in_stride < F || out_stride < F)
+    return ppo_fail("ppo_carla_debug_ln_backward: n and F must be positive, strides at least F", -1);
+  if (int rc = ppo_runtime_check()) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = nullptr;
+  const size_t part_cap = ln_part_floats(n, F);
+  if (hipMalloc((void**)&part, part_cap * sizeof(float)) != hipSuccess)
+    return ppo_fail("ppo_carla_debug_ln_backward: device allocation failed", -2);
+  const long tot = (long)n * F;
+  hipLaunchKernelGGL(k_carla_ln_mask, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, dy, y, out_stride, n, F,
+                     dz);
+  const int fit = launch_ln_bwd(n, F, dz, F, z, in_stride, gamma, stat, dgamma, dbeta, part, part_cap, s);
+  const bool ok = fit == 0 && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  (void)hipFree(part);
+  return ok ? 0 : ppo_fail("ppo_carla_debug_ln_backward: launch failed", -2);
 }

@@ -1,5 +1,6 @@
 // ppo_pth.hip — C-ABI of include/ppo_pth.h: the reference agents' module structure as pth::Spec
 // over the flat layouts, and the archive reader/writer of pth_io.hpp. Host code only.
+#include <algorithm>
 #include <exception>
 #include <string>
 #include <vector>
@@ -96,6 +97,54 @@ pth::Spec carla_spec(const ppo_carla_layout& L) {
   return s;
 }
 
+// carla_model.h:44-192 for any ppo_carla_arch: a LayerNorm child after each normalised Conv2d / Linear
+// shifts the Sequential indices (Conv LN ReLU: 3i, 3i + 1; Linear LN ReLU: 0, 1, 3, 4, 6). Tensors
+// are pushed in the layout's named_parameters() order.
+pth::Spec carla_spec2(const ppo_carla_layout2& L) {
+  pth::Spec s;
+  s.P = L.P;
+  const int eln = L.arch.encoder_ln, mln = L.arch.mlp_ln, pln = L.arch.policy_ln;
+  seq(s, "cnn", (eln ? 3 : 2) * PPO_CARLA_NCONV);
+  seq(s, "linear", mln ? 6 : 4);
+  seq(s, "state_linear", mln ? 6 : 4);
+  seq(s, "value_head", mln ? 7 : 5);
+  seq(s, "policy_head", pln ? 6 : 4);
+  seq(s, "dist_mu", 1);
+  seq(s, "dist_sigma", 1);
+  s.tensors.push_back({"action_space_high", Shape{}, L.hi, false});
+  s.tensors.push_back({"action_space_low", Shape{}, L.lo, false});
+  for (int i = 0; i < PPO_CARLA_NCONV; ++i) {
+    const int step = eln ? 3 : 2;
+    const std::string n = "cnn." + std::to_string(step * i);
+    s.tensors.push_back({n + ".weight", Shape{L.conv_oc[i], L.conv_ic[i], L.conv_k[i], L.conv_k[i]}, L.conv_w[i], true});
+    s.tensors.push_back({n + ".bias", Shape{L.conv_oc[i]}, L.conv_b[i], true});
+    if (eln) {
+      const std::string m = "cnn." + std::to_string(step * i + 1);
+      const Shape shp{L.conv_oc[i], L.conv_oh[i], L.conv_ow[i]};
+      s.tensors.push_back({m + ".weight", shp, L.conv_g[i], true});
+      s.tensors.push_back({m + ".bias", shp, L.conv_be[i], true});
+    }
+  }
+  // a Sequential of Linear [LayerNorm] ReLU pairs: layer k at index k * (ln ? 3 : 2)
+  auto mlp = [&](const std::string& name, int ln, int k, long w, long b, long g, long be, int out, int in) {
+    const int at = k * (ln ? 3 : 2);
+    linear(s, name + "." + std::to_string(at), w, b, out, in);
+    if (ln && g >= 0) norm(s, name + "." + std::to_string(at + 1), g, be, out);
+  };
+  mlp("linear", mln, 0, L.lin_w[0], L.lin_b[0], L.lin_g[0], L.lin_be[0], 512, 1024 + 256);
+  mlp("linear", mln, 1, L.lin_w[1], L.lin_b[1], L.lin_g[1], L.lin_be[1], 256, 512);
+  mlp("state_linear", mln, 0, L.st_w[0], L.st_b[0], L.st_g[0], L.st_be[0], 256, L.NM);
+  mlp("state_linear", mln, 1, L.st_w[1], L.st_b[1], L.st_g[1], L.st_be[1], 256, 256);
+  mlp("value_head", mln, 0, L.v_w[0], L.v_b[0], L.v_g[0], L.v_be[0], 256, 256 + L.NV);
+  mlp("value_head", mln, 1, L.v_w[1], L.v_b[1], L.v_g[1], L.v_be[1], 256, 256);
+  mlp("value_head", mln, 2, L.v_w[2], L.v_b[2], -1, -1, 1, 256);
+  mlp("policy_head", pln, 0, L.pi_w[0], L.pi_b[0], L.pi_g[0], L.pi_be[0], 256, 256);
+  mlp("policy_head", pln, 1, L.pi_w[1], L.pi_b[1], L.pi_g[1], L.pi_be[1], 256, 256);
+  linear(s, "dist_mu.0", L.mu_w, L.mu_b, L.A, 256);
+  linear(s, "dist_sigma.0", L.sg_w, L.sg_b, L.A, 256);
+  return s;
+}
+
 // the spec must tile the layout exactly (guards a layout / spec drift)
 bool covers(const pth::Spec& s) {
   long total = 0;
@@ -128,6 +177,34 @@ extern "C" int ppo_carla_layout_fill(ppo_carla_layout* L, int C, int IH, int IW,
   if (!L || ppo_carla_layout_init(L, C, IH, IW, NM, NV, A) != 0)
     return ppo_fail("ppo_carla_layout_fill: bad arguments (n_flatten must be 256 * 2 * 2)", -1);
   return 0;
+}
+
+extern "C" int ppo_carla_layout2_fill(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
+                                      const ppo_carla_arch* arch) {
+  if (!L) return ppo_fail("ppo_carla_layout2_fill: null argument", -1);
+  if (arch && (arch->encoder_ln < 0 || arch->encoder_ln > 1))
+    return ppo_fail("ppo_carla_layout2_fill: encoder_ln must be 0 (roach) or 1 (roach_ln); roach_ln2 is not built", -1);
+  const int rc = ppo_carla_layout2_init(L, C, IH, IW, NM, NV, A, arch);
+  if (rc == -2)
+    return ppo_fail("ppo_carla_layout2_fill: the roach_ln encoder needs a 192 x 192 bev: the reference hard-codes its "
+                    "LayerNorm shapes (carla_model.h:45-62)", -1);
+  if (rc != 0) return ppo_fail("ppo_carla_layout2_fill: bad arguments (n_flatten must be 256 * 2 * 2)", -1);
+  return 0;
+}
+
+extern "C" int ppo_carla_tensor_name(const ppo_carla_layout2* L, int t, char* buf, int len) {
+  if (!L || !buf || len <= 0) return ppo_fail("ppo_carla_tensor_name: null argument", -1);
+  if (t < 0 || t >= L->ntensors) return ppo_fail("ppo_carla_tensor_name: tensor index out of range", -1);
+  return guarded([&] {
+    const pth::Spec s = carla_spec2(*L);
+    if ((int)s.tensors.size() != L->ntensors || s.tensors[t].off != L->t_off[t])
+      return ppo_fail("ppo_carla_tensor_name: layout does not match the agent structure", -1);
+    const std::string& nm = s.tensors[t].name;
+    const size_t k = std::min(nm.size(), (size_t)len - 1);
+    std::copy(nm.begin(), nm.begin() + k, buf);
+    buf[k] = 0;
+    return 0;
+  });
 }
 
 extern "C" int ppo_pth_save_agent(const ppo_layout* L, const float* params, const char* path) {
@@ -196,6 +273,30 @@ extern "C" int ppo_carla_pth_load(const ppo_carla_layout* L, const char* path, f
   return guarded([&] {
     const pth::Spec s = carla_spec(*L);
     if (!covers(s)) return ppo_fail("ppo_carla_pth_load: layout does not match the agent structure", -1);
+    const std::vector<float> flat = pth::load_module(path, s);
+    std::copy(flat.begin(), flat.end(), params);
+    return 0;
+  });
+}
+
+extern "C" int ppo_carla_pth_save2(const ppo_carla_layout2* L, const float* params, const char* path) {
+  if (!L || !params || !path) return ppo_fail("ppo_carla_pth_save2: null argument", -1);
+  return guarded([&] {
+    const pth::Spec s = carla_spec2(*L);
+    if (!covers(s)) return ppo_fail("ppo_carla_pth_save2: layout does not match the agent structure", -1);
+    pth::save_module(path, s, params);
+    return 0;
+  });
+}
+
+// torch::load into a module of another arch fails on the first parameter the archive lacks (a
+// LayerNorm child where the layout expects none holds a ReLU, and the other way round), by name
+extern "C" int ppo_carla_pth_load2(const ppo_carla_layout2* L, const char* path, float* params, long n) {
+  if (!L || !params || !path) return ppo_fail("ppo_carla_pth_load2: null argument", -1);
+  if (n != L->P) return ppo_fail("ppo_carla_pth_load2: n != layout P", -1);
+  return guarded([&] {
+    const pth::Spec s = carla_spec2(*L);
+    if (!covers(s)) return ppo_fail("ppo_carla_pth_load2: layout does not match the agent structure", -1);
     const std::vector<float> flat = pth::load_module(path, s);
     std::copy(flat.begin(), flat.end(), params);
     return 0;

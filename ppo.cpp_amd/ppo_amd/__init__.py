@@ -95,6 +95,32 @@ class CarlaLayout(C.Structure):  # include/ppo_carla.h
                 ("t_grad", C.c_int * MAX_CT)]
 
 
+MAX_CT2 = 64
+
+
+class CarlaArch(C.Structure):  # ppo_carla_arch: all zero = the roach encoder without LayerNorm
+    _fields_ = [("encoder_ln", C.c_int), ("mlp_ln", C.c_int), ("policy_ln", C.c_int)]
+
+
+class CarlaLayout2(C.Structure):  # ppo_carla_layout2: CarlaLayout + the LayerNorm tensors' offsets (-1: none)
+    _fields_ = CarlaLayout._fields_[:-4] + [
+        ("arch", CarlaArch),
+        ("conv_g", C.c_long * NCONV), ("conv_be", C.c_long * NCONV),
+        ("lin_g", C.c_long * 2), ("lin_be", C.c_long * 2), ("st_g", C.c_long * 2), ("st_be", C.c_long * 2),
+        ("v_g", C.c_long * 2), ("v_be", C.c_long * 2), ("pi_g", C.c_long * 2), ("pi_be", C.c_long * 2),
+        ("ntensors", C.c_int), ("t_off", C.c_long * MAX_CT2), ("t_len", C.c_long * MAX_CT2),
+        ("t_grad", C.c_int * MAX_CT2)]
+
+    def tensor_names(self):
+        """named_parameters() names, in t_off order"""
+        buf = C.create_string_buffer(64)
+        out = []
+        for t in range(self.ntensors):
+            check(lib().ppo_carla_tensor_name(C.byref(self), t, buf, len(buf)))
+            out.append(buf.value.decode())
+        return out
+
+
 class CarlaTrainConfig(C.Structure):  # ppo_carla_train_config; defaults = carla_config.h:31-40
     _fields_ = [("clip_coef", C.c_float), ("ent_coef", C.c_float), ("vf_coef", C.c_float),
                 ("max_grad_norm", C.c_float), ("adam_eps", C.c_float), ("norm_adv", C.c_int), ("clip_vloss", C.c_int)]
@@ -214,6 +240,14 @@ SYMBOLS = [
                                C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("ppo_carla_pth_save", _I, [C.POINTER(CarlaLayout), _FP, C.c_char_p]),
     ("ppo_carla_pth_load", _I, [C.POINTER(CarlaLayout), C.c_char_p, _FP, _L]),
+    ("ppo_carla_create2", _I, [C.POINTER(CarlaConfig), C.POINTER(CarlaArch), _I, C.c_char_p, C.POINTER(_VP)]),
+    ("ppo_carla_get_layout2", _I, [_VP, C.POINTER(CarlaLayout2)]),
+    ("ppo_carla_layout2_fill", _I, [C.POINTER(CarlaLayout2), _I, _I, _I, _I, _I, _I, C.POINTER(CarlaArch)]),
+    ("ppo_carla_tensor_name", _I, [C.POINTER(CarlaLayout2), _I, C.c_char_p, _I]),
+    ("ppo_carla_pth_save2", _I, [C.POINTER(CarlaLayout2), _FP, C.c_char_p]),
+    ("ppo_carla_pth_load2", _I, [C.POINTER(CarlaLayout2), C.c_char_p, _FP, _L]),
+    ("ppo_carla_debug_ln_forward", _I, [_I, _I, _FP, _L, _FP, _FP, _FP, _L, _FP, _VP]),
+    ("ppo_carla_debug_ln_backward", _I, [_I, _I, _FP, _L, _FP, _FP, _FP, _L, _FP, _FP, _FP, _FP, _VP]),
 ]
 
 
@@ -256,6 +290,21 @@ def agent_layout(kind, O, A, H) -> Layout:
 def carla_layout(C_=15, IH=192, IW=192, NM=8, NV=3, A=2) -> CarlaLayout:
     L = CarlaLayout()
     check(lib().ppo_carla_layout_fill(C.byref(L), C_, IH, IW, NM, NV, A))
+    return L
+
+
+def carla_arch(encoder="roach", layer_norm=False, policy_layer_norm=True) -> CarlaArch:
+    """image_encoder / use_layer_norm / use_layer_norm_policy_head of carla_config.h as a CarlaArch"""
+    if encoder not in ("roach", "roach_ln"):
+        raise PPOError(f"Unsupported image_encoder chosen. Options roach, roach_ln. Chosen option: {encoder}")
+    return CarlaArch(int(encoder == "roach_ln"), int(bool(layer_norm)), int(bool(layer_norm and policy_layer_norm)))
+
+
+def carla_layout2(C_=15, IH=192, IW=192, NM=8, NV=3, A=2, encoder="roach", layer_norm=False,
+                  policy_layer_norm=True) -> CarlaLayout2:
+    L = CarlaLayout2()
+    arch = carla_arch(encoder, layer_norm, policy_layer_norm)
+    check(lib().ppo_carla_layout2_fill(C.byref(L), C_, IH, IW, NM, NV, A, C.byref(arch)))
     return L
 
 
@@ -303,6 +352,18 @@ def save_carla_pth(layout: CarlaLayout, params, path):
 def load_carla_pth(layout: CarlaLayout, path):
     out = np.empty(layout.P, np.float32)
     check(lib().ppo_carla_pth_load(C.byref(layout), os.fsencode(path), out.ctypes.data, layout.P))
+    return out
+
+
+def save_carla_pth2(layout: CarlaLayout2, params, path):
+    """torch::save of the CaRL agent of layout.arch (LayerNorm children at the reference's indices)"""
+    p = _f32(params, layout.P)
+    check(lib().ppo_carla_pth_save2(C.byref(layout), p.ctypes.data, os.fsencode(path)))
+
+
+def load_carla_pth2(layout: CarlaLayout2, path):
+    out = np.empty(layout.P, np.float32)
+    check(lib().ppo_carla_pth_load2(C.byref(layout), os.fsencode(path), out.ctypes.data, layout.P))
     return out
 
 
@@ -652,14 +713,27 @@ class CarlaAgent:
     _MODES = {"sample": PPO_CARLA_SAMPLE, "mean": PPO_CARLA_MEAN, "roach": PPO_CARLA_ROACH}
 
     def __init__(self, max_batch, obs_channels=15, bev=192, num_measurements=8, num_value_measurements=3,
-                 action_dim=2, beta_min=1.0, seed=1, rank=0, device=0, options: str | None = None):
+                 action_dim=2, beta_min=1.0, seed=1, rank=0, device=0, options: str | None = None,
+                 encoder="roach", layer_norm=False, policy_layer_norm=True):
+        """encoder "roach" | "roach_ln", layer_norm (use_layer_norm), policy_layer_norm
+        (use_layer_norm_policy_head): carla_model.h:44-64, :113-175. The default agent's `layout` is a
+        CarlaLayout, a LayerNorm agent's a CarlaLayout2; `layout2` is a CarlaLayout2 for both."""
         self.cfg = CarlaConfig(obs_channels, bev, bev, num_measurements, num_value_measurements, action_dim, beta_min,
                                max_batch, seed, rank)
         self._h = C.c_void_p()
-        check(lib().ppo_carla_create_ex(C.byref(self.cfg), device, options.encode() if options else None,
-                                        C.byref(self._h)))
-        self.layout = CarlaLayout()
-        check(lib().ppo_carla_get_layout(self._h, C.byref(self.layout)))
+        self.arch = carla_arch(encoder, layer_norm, policy_layer_norm)
+        opts = options.encode() if options else None
+        if self.arch.encoder_ln or self.arch.mlp_ln:
+            check(lib().ppo_carla_create2(C.byref(self.cfg), C.byref(self.arch), device, opts, C.byref(self._h)))
+        else:
+            check(lib().ppo_carla_create_ex(C.byref(self.cfg), device, opts, C.byref(self._h)))
+        self.layout2 = CarlaLayout2()
+        check(lib().ppo_carla_get_layout2(self._h, C.byref(self.layout2)))
+        if self.arch.encoder_ln or self.arch.mlp_ln:
+            self.layout = self.layout2
+        else:
+            self.layout = CarlaLayout()
+            check(lib().ppo_carla_get_layout(self._h, C.byref(self.layout)))
 
     def close(self):
         if self._h:
@@ -729,6 +803,29 @@ class CarlaAgent:
 
     def comm_broadcast_params(self, root=0):
         check(lib().ppo_carla_comm_broadcast_params(self._h, root))
+
+
+def carla_ln_forward(z: "DeviceArray", gamma: "DeviceArray", beta: "DeviceArray", n, F, in_stride=None,
+                     out_stride=None):
+    """ppo_carla_debug_ln_forward: (y [n, out_stride], stat [n, 2]) = the agent's LayerNorm + ReLU launch
+    on rows z[r * in_stride : r * in_stride + F]; y's columns beyond F are left zero."""
+    in_stride, out_stride = in_stride or F, out_stride or F
+    y, stat = DeviceArray((n, out_stride)), DeviceArray((n, 2))
+    check(lib().ppo_memset_dev(y.ptr, 0, 4 * n * out_stride))
+    check(lib().ppo_carla_debug_ln_forward(n, F, z.ptr, in_stride, gamma.ptr, beta.ptr, y.ptr, out_stride, stat.ptr,
+                                           None))
+    return y, stat
+
+
+def carla_ln_backward(z: "DeviceArray", gamma: "DeviceArray", stat: "DeviceArray", y: "DeviceArray",
+                      dy: "DeviceArray", n, F, in_stride=None, out_stride=None):
+    """ppo_carla_debug_ln_backward: (dz [n, F], dgamma [F], dbeta [F]) from dy [n, F] (dense), the forward's
+    z / stat and its output y (the ReLU mask)."""
+    in_stride, out_stride = in_stride or F, out_stride or F
+    dz, dg, db = DeviceArray((n, F)), DeviceArray((F,)), DeviceArray((F,))
+    check(lib().ppo_carla_debug_ln_backward(n, F, z.ptr, in_stride, gamma.ptr, stat.ptr, y.ptr, out_stride, dy.ptr,
+                                            dz.ptr, dg.ptr, db.ptr, None))
+    return dz, dg, db
 
 
 class SynthEnv:

@@ -3,7 +3,9 @@
 [n, 15, 192, 192], 8 measurements, 3 value measurements, 2 actions) on one GPU: samples/s of
 ppo_carla_forward with inputs resident in HBM, and the algorithmic MFMA rate (87.9 MFLOP per sample,
 SURVEY §8d), and of the PPO minibatch update (ppo_carla_update, counted as 3x the forward:
-forward + two backward GEMMs per layer)."""
+forward + two backward GEMMs per layer). --encoder roach_ln / --layer-norm time the LayerNorm variants
+(ppo_carla_create2); their parameters come from tests/carla_ln_ref.py's init_params (LayerNorm weights
+U(0.5, 1.5)), as the default agent's come from tests/carla_inputs.py."""
 import argparse
 import json
 import os
@@ -27,12 +29,20 @@ def main():
     ap.add_argument("--update-batch", type=int, nargs="*", default=[256, 2048])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--options", default="", help="ppo_carla_create_ex options, e.g. tail=layers")
+    ap.add_argument("--encoder", default="roach", choices=["roach", "roach_ln"], help="image_encoder")
+    ap.add_argument("--layer-norm", action="store_true", help="use_layer_norm (with the policy head's)")
     args = ap.parse_args()
     ppo_amd.set_device(0)
-    L = CI.layout()
-    p = CI.params(L)
+    arch = dict(encoder=args.encoder, layer_norm=args.layer_norm)
+    if args.encoder == "roach" and not args.layer_norm:
+        L = CI.layout()
+        p = CI.params(L)
+    else:
+        import carla_ln_ref as LR
+        L = ppo_amd.carla_layout2(**arch)
+        p = LR.init_params(L, CI)
     for n in args.batch:
-        ag = ppo_amd.CarlaAgent(max_batch=n, options=args.options or None)
+        ag = ppo_amd.CarlaAgent(max_batch=n, options=args.options or None, **arch)
         ag.load_params(p)
         bev, meas, vmeas, _ = CI.inputs(n)
         d = [ppo_amd.DeviceArray.from_numpy(bev, np.uint8), ppo_amd.DeviceArray.from_numpy(meas),
@@ -52,12 +62,12 @@ def main():
             ag.forward(*d, sample_type="sample", step_id=i, out=out, sync=False)
         ppo_amd.lib().ppo_device_sync()
         dd = (time.perf_counter() - t0) / args.iters
-        print(json.dumps({"workload": "carla_forward", "batch": n, "options": args.options, "ms_per_forward": round(dt * 1e3, 3),
+        print(json.dumps({"workload": "carla_forward", "batch": n, "options": args.options, **arch, "ms_per_forward": round(dt * 1e3, 3),
                           "ms_per_forward_back_to_back": round(dd * 1e3, 3), "samples_per_s": round(n / dt, 1),
                           "tflops": round(n * FLOP_PER_SAMPLE / dt / 1e12, 2)}), flush=True)
         ag.close()
     for n in args.update_batch:
-        ag = ppo_amd.CarlaAgent(max_batch=n, options=args.options or None)
+        ag = ppo_amd.CarlaAgent(max_batch=n, options=args.options or None, **arch)
         ag.load_params(p)
         rng = np.random.default_rng(1)
         bev = rng.integers(0, 256, size=(n, 15, 192, 192), dtype=np.uint8)
@@ -73,7 +83,7 @@ def main():
             ag.update(*d, want_stats=False)
         ppo_amd.lib().ppo_device_sync()
         dt = (time.perf_counter() - t0) / its
-        print(json.dumps({"workload": "carla_update", "batch": n, "options": args.options, "ms_per_update": round(dt * 1e3, 3),
+        print(json.dumps({"workload": "carla_update", "batch": n, "options": args.options, **arch, "ms_per_update": round(dt * 1e3, 3),
                           "samples_per_s": round(n / dt, 1),
                           "tflops": round(3 * n * FLOP_PER_SAMPLE / dt / 1e12, 2)}), flush=True)
         ag.close()
