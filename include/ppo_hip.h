@@ -136,6 +136,12 @@ int ppo_create(const ppo_hip_config* cfg, int device, ppo_t** out);
  *   h1_handoff=auto|store|recompute  the H1 rows of k_upd's hand-off: stored by k_upd (store, auto) or
  *                            recomputed inside the fused split-bf16 dW from Xn, W1 and 8 bytes of LayerNorm
  *                            statistics per row (recompute: bitwise the stored rows; measured slower overall)
+ *   dw_stage=auto|dma|split_once  staging of the fused split-bf16 dW (hidden 256, obs_dim <= 32, dw_mfma
+ *                            bf16x6/x8/x9, h1_handoff=store): LDS-DMA stages of fp32 rows that every consuming
+ *                            wave splits for itself (dma: k_dwf_bx), or register-staged loads split once per
+ *                            workgroup into bf16 piece images read with transposed LDS reads (split_once:
+ *                            k_dwf_so; bitwise the same dW, measured faster; auto where it applies).
+ *                            split_once where it does not apply fails
  *   values_mfma=auto|bx6|f32 the rollout's critic pass (values of the stored rows and the bootstrap,
  *                            ac:655 / :761): k_vbx, layer 2 as k_upd's six split-bf16 piece products
  *                            (bx6; auto where upd_mfma=bx6 applies: the per-step act kernels then skip
@@ -260,6 +266,10 @@ int ppo_get_device(const ppo_t* ctx, int* device, char* pci_bus_id, int len);
  * e.g. "update=k_upd/bx6 dw=k_dwf_dma/f32" (bx6: k_upd's 256-wide GEMMs as split-bf16 piece
  * products, upd_mfma). NUL-terminated, truncated to len. */
 int ppo_kernel_info(const ppo_t* ctx, char* buf, int len);
+/* The piece image of the split-once dW (dw_stage=split_once): byte offset, inside one bf16 piece's 8 KB
+ * image of a 16-row x 256-column stage source, of the four values of row `row` (0..15), columns col ..
+ * col + 3 (col a multiple of 4 in 0..252); -1 outside. Host arithmetic only (tests of the image). */
+int ppo_dw_image_offset(int row, int col);
 
 /* ---- device memory helpers (so C / ctypes callers need no HIP headers) ---- */
 int ppo_set_device(int device);

@@ -202,6 +202,7 @@ struct ppo_ctx {
   int dw_fused = 1;
   int dw_dma = 1;                       // create option dw_dma: k_dwf stages by LDS DMA (k_dwf_dma)
   int dw_bx = 0;                        // create option dw_mfma: 0 fp32 MFMA, 8 / 9 exact bf16 piece products (k_dwf_bx)
+  int dw_so = 0;                        // create option dw_stage: k_dwf_bx's split-once form (k_dwf_so)
   int rollout_mode = PPO_ROLLOUT_AUTO;  // ppo_set_rollout_mode
   int gradstep = 0;                     // create option gradstep=fused|split (default split)
   unsigned* gs_bar = nullptr;           // k_gradstep's grid barrier counter
@@ -304,6 +305,7 @@ struct CreateOptions {
   int values_mfma = -1;  // values_mfma=auto (bx6 where k_upd's bx6 pieces exist) | f32 | bx6
   int upd_split = 0;     // upd_split=auto|1|2|4|8: minibatch rows per k_upd + dW launch pair (M / n)
   int h1_handoff = -1;   // h1_handoff=auto|store|recompute: H1 rows from k_upd, or recomputed by k_dwf_bx
+  int dw_stage = -1;     // dw_stage=auto|dma|split_once: k_dwf_bx (LDS-DMA stages, split per consumer) or k_dwf_so
   // 1: ppo_update replays its minibatch launches as one captured hipGraph; 0 (default): eager.
   // Snapshots work with it on (ppo_read_snapshot waits for the snapshot's event on the host).
   int update_graph = -1;  // -1 auto (kUpdGraphAutoRows), 0 eager, 1 graph
@@ -340,6 +342,12 @@ static int kUpdSplitAuto(int M) { (void)M; return 1; }
 // stored_h1) took k_upd 0.605 -> 0.573 ms per launch but k_dwf_bx 217 -> 255 us (its extra fp32 MFMAs and a
 // barrier per stage): 15.97 -> 16.04 ms per metric iteration (profiles/r06/h1_recompute/)
 static constexpr bool kH1RecomputeAuto = false;
+// dw_stage=auto: the split-once form (k_dwf_so, bitwise k_dwf_bx's dW: test_gpu_dw_split_once) wherever it
+// applies. Against the parent's k_dwf_bx on the same box, interleaved runs: dW 3.46 -> 2.98 ms per metric
+// iteration (216 -> 186 us per launch), the iteration 15.62-15.80 -> 15.17-15.28 ms (2-3.7 % on four boxes,
+// every run of it faster than every run of k_dwf_bx on its box); the E = 512 shard unchanged, 3.40-3.41 ->
+// 3.39-3.41 ms (profiles/r07/dw_split_once/)
+static constexpr bool kDwSplitOnceAuto = true;
 static constexpr int kUpdGraphAutoRows = 4096;  // update_graph=auto: minibatches of at most this many rows
 // gradnorm=auto: k_gradnorm. The fold measured slower everywhere (E = 512 shard 3.44 -> 3.78 ms, cfg2 87.5 -> 88.7,
 // cfg1 17.4 -> 17.9: each tile's write-through store + counter round trip costs more than the launch it
@@ -373,6 +381,8 @@ static int parse_create_options(const char* opts, CreateOptions* o) {
     else if (k == "gae" && (v == "auto" || v == "serial" || v == "scan")) o->gae_scan = v == "auto" ? -1 : v == "scan";
     else if (k == "h1_handoff" && (v == "auto" || v == "store" || v == "recompute"))
       o->h1_handoff = v == "auto" ? -1 : v == "recompute";
+    else if (k == "dw_stage" && (v == "auto" || v == "dma" || v == "split_once"))
+      o->dw_stage = v == "auto" ? -1 : v == "split_once";
     else if (k == "upd_split" && (v == "auto" || v == "1" || v == "2" || v == "4" || v == "8"))
       o->upd_split = v == "auto" ? 0 : v[0] - '0';
     else if (k == "values_mfma" && (v == "auto" || v == "f32" || v == "bx6"))
@@ -616,6 +626,15 @@ extern "C" int ppo_create_ex(const ppo_hip_config* cfg, int device, const char* 
     c->h1_recomp = rc_ok && (opt.h1_handoff == 1 || (opt.h1_handoff < 0 && kH1RecomputeAuto));
     if (c->h1_recomp)
       for (int k = 0; k < 2; ++k) rc |= dmalloc(&c->LNS[k], 2 * (size_t)c->M);
+    // the split-once form covers k_dwf_bx's non-recompute template space (launch_dw's fused dispatch)
+    const bool so_ok = !c->use_upd2 && H == 256 && (OP == 16 || OP == 32) && c->dw_fused && c->dw_dma && c->dw_bx &&
+                       !c->h1_recomp;
+    if (opt.dw_stage == 1 && !so_ok) {
+      ppo_destroy(c);
+      return fail("ppo_create: dw_stage=split_once needs the fused split-bf16 dW (hidden 256, obs_dim <= 32, dw_mfma "
+                  "bf16x6/x8/x9) with h1_handoff=store");
+    }
+    c->dw_so = so_ok && (opt.dw_stage == 1 || (opt.dw_stage < 0 && kDwSplitOnceAuto));
   }
   for (int k = 0; k < 2; ++k) rc |= dmalloc(&c->dwslab[k], (size_t)c->msplit * c->nchunks * (H * H + H * OP));
   if (c->upd2_split) rc |= dmalloc(&c->Z1, Mr * 128);
@@ -1086,6 +1105,7 @@ extern "C" int ppo_update_ex(ppo_t* c, float lr, int nsteps, const int32_t* perm
   dw.dma = c->dw_dma;
   dw.bx = c->dw_dma ? c->dw_bx : 0;
   dw.h1_recompute = c->h1_recomp;
+  dw.split_once = c->dw_so;
   dw.kl1 = (c->K.O == 16 * (c->K.OP / 16 - 1) + 1) ? 1 : 4;
   dw.xn = c->Xn;
   dw.obs = c->buf[PPO_BUF_OBS];
@@ -1532,7 +1552,7 @@ extern "C" int ppo_kernel_info(const ppo_t* c, char* buf, int len) {
   const bool fused = c->dw_fused && H == 256 && (OP == 16 || OP == 32);  // launch_dw's dispatch
   const std::string bxs = c->dw_bx ? "/bf16x" + std::to_string(c->dw_bx) : "/f32";
   std::string dw = c->use_upd2 ? (c->dw_dma && OP == 384 && c->K.O % 4 == 0 ? "k_dw2_dma" + bxs : "k_dw2")
-                   : fused ? (!c->dw_dma ? "k_dwf" : c->dw_bx ? "k_dwf_bx/bf16x" + std::to_string(c->dw_bx) + (c->h1_recomp ? "/h1rc" : "")
+                   : fused ? (!c->dw_dma ? "k_dwf" : c->dw_bx ? "k_dwf_bx/bf16x" + std::to_string(c->dw_bx) + (c->h1_recomp ? "/h1rc" : c->dw_so ? "/split_once" : "")
                                                         : "k_dwf_dma/f32")
                    : (c->dw_dma && H == 256 && OP == 112) ? "k_dw_dma" + bxs
                                                           : "k_dw";
@@ -1542,6 +1562,10 @@ extern "C" int ppo_kernel_info(const ppo_t* c, char* buf, int len) {
                         (c->gn_fold && !c->gradstep ? " norm=k_colsum" : c->gradstep ? " norm=k_gradstep" : " norm=k_gradnorm");
   snprintf(buf, (size_t)len, "%s", s.c_str());
   return 0;
+}
+
+extern "C" int ppo_dw_image_offset(int row, int col) {
+  return row < 0 || row >= 16 || col < 0 || col >= 256 || (col & 3) ? -1 : dwso_off(row, col);
 }
 
 extern "C" int ppo_set_device(int d) {

@@ -1507,6 +1507,242 @@ __global__ __launch_bounds__(512) void k_dwf_bx(DwArgs a) {
 }
 
 // =============================================================================================
+// k_dwf_so — k_dwf_bx's split-once form (create option dw_stage=split_once): the same piece products
+// in the same order (bitwise k_dwf_bx's dW), but every staged fp32 value is split once per workgroup
+// instead of once per consuming wave (k_dwf_bx: 64 split3 per workgroup and stage where 25 cover every
+// element).
+//   Staging: each thread loads its share of the stage after next into registers (buffer_load_dwordx4:
+// 6 float4 of DZ2 | H1 | DZ1 and one of Xn, which only the first NXI waves have; rows >= m1 read as zero
+// through the out-of-range offset), splits them with split3_pair between the MFMAs of the current stage and
+// stores the three bf16 pieces (ds_write_b64 each) into the other of two piece images; one barrier per stage.
+//   Image (DwsoGeo): per source and piece a row-major [16][256] bf16 image addressed through dwso_off,
+// Xn as plain [16][32] bf16 rows (columns >= OP stay zero). A wave's MFMA operand — lane (r, h): rows
+// 8 h .. 8 h + 7 of column r — is two ds_read_b64_tr_b16 per piece (rows 8 h + 4 j .. + 3, j = 0 / 1):
+// lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3 of the group's 4 x 16 block and
+// receives its own column's four rows. Every transposed read of a 32-lane half covers 256 contiguous
+// bytes: conflict-free. EXEC is all ones at every read (whole waves only).
+// =============================================================================================
+template <int OP>
+struct DwsoGeo {
+  static constexpr int PIECE = 16 * 256 * 2;  // bytes: one piece of one 16 x 256 source
+  static constexpr int SRC = 3 * PIECE;       // hi | mid | lo
+  static constexpr int oXN = 3 * SRC;         // DZ2 | H1 | DZ1, then Xn
+  static constexpr int XPIECE = 16 * 32 * 2;
+  static constexpr int IMG = oXN + 3 * XPIECE;
+  static constexpr int total = 2 * IMG;             // bytes
+  static constexpr int SPILL = 2 * XPIECE + 64 * 8;  // behind the images: where the waves without an Xn share store
+  static constexpr int lds = total + SPILL;
+};
+// A/B switches of k_dwf_so's stage loop (profiles/r07/dw_split_once/): PPO_DWSO_SGB = 1 places a quarter of the
+// next stage's split and stores and the next H1 operand's reads between the 12 MFMAs of each H1 column block
+// with sched_group_barrier, fenced per block (0: the compiler's own order, which splits in clumps between the
+// blocks: dW 3.22 -> 3.00 ms per metric iteration, with SGB 2.80-2.98). Unfenced, the pattern pulled the splits
+// in front of the stage's first MFMA, onto the wait for the loads: slower than k_dwf_bx.
+// PPO_DWSO_RELOAD = 1 reloads a source's registers right after their split (a full stage in flight) instead of
+// at the stage's end: dW 2.8-2.9 ms, but on one of three boxes k_upd ran 4 % slower beside it and the iteration
+// no faster than k_dwf_bx's; 0 won on every box. PPO_DWSO_PRIO = 1 raises the priority of waves 4..7 (one of
+// the two waves of every SIMD): no change.
+#ifndef PPO_DWSO_SGB
+#define PPO_DWSO_SGB 1
+#endif
+#ifndef PPO_DWSO_PRIO
+#define PPO_DWSO_PRIO 0
+#endif
+#ifndef PPO_DWSO_RELOAD
+#define PPO_DWSO_RELOAD 0
+#endif
+typedef short dwso_v4s __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+PPO_DEV u32x2 lds_read_tr16(const unsigned char* p) {
+  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) dwso_v4s*)p));
+}
+// one 32x32x16 operand's three pieces: p0 / p1 = this lane's addresses of its rows 8 h .. + 3 / 8 h + 4 .. + 7
+// in the hi piece; the pieces are STRIDE bytes apart
+template <int STRIDE>
+PPO_DEV Split3 dwso_operand(const unsigned char* p0, const unsigned char* p1) {
+  Split3 s;
+  const u32x2 h0 = lds_read_tr16(p0), h1 = lds_read_tr16(p1);
+  const u32x2 m0 = lds_read_tr16(p0 + STRIDE), m1 = lds_read_tr16(p1 + STRIDE);
+  const u32x2 l0 = lds_read_tr16(p0 + 2 * STRIDE), l1 = lds_read_tr16(p1 + 2 * STRIDE);
+  s.hi = u32x4{h0[0], h0[1], h1[0], h1[1]};
+  s.mid = u32x4{m0[0], m0[1], m1[0], m1[1]};
+  s.lo = u32x4{l0[0], l0[1], l1[0], l1[1]};
+  return s;
+}
+// four staged values -> their pieces, 8 bytes each, at p, p + STRIDE, p + 2 STRIDE
+template <int STRIDE>
+PPO_DEV void dwso_split_store(unsigned char* p, f4 x) {
+  unsigned h0, m0, l0, h1, m1, l1;
+  split3_pair(x[0], x[1], h0, m0, l0);
+  split3_pair(x[2], x[3], h1, m1, l1);
+  *reinterpret_cast<u32x2*>(p) = u32x2{h0, h1};
+  *reinterpret_cast<u32x2*>(p + STRIDE) = u32x2{m0, m1};
+  *reinterpret_cast<u32x2*>(p + 2 * STRIDE) = u32x2{l0, l1};
+}
+template <int H, int OP, int NSL, int NP>
+__global__ __launch_bounds__(512) void k_dwf_so(DwArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
+  using GE = DwsoGeo<OP>;
+  constexpr int KS = 16;
+  static_assert(H == 256 && (OP == 16 || OP == 32), "k_dwf_so geometry");
+  constexpr int NXI = KS * OP / 256;
+  constexpr int TOW = 2 / NSL, TIW = 4;
+  static_assert(NSL == 1 || NSL == 2, "k_dwf slices");
+  static_assert(NP == 6 || NP == 8 || NP == 9, "k_dwf_so passes");
+  static_assert(GE::lds <= 160 * 1024, "k_dwf_so LDS");
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l32 = lane & 31,
+            hs = lane >> 5;
+  const int wo = wave & 3, wi = wave >> 2;
+  const int trunk = blockIdx.y, slice = NSL > 1 ? (int)blockIdx.z : 0;
+  const int obase = slice * (H / NSL);
+  const bool w1_wave = NSL == 1 || wave < 8 / NSL;
+  const int w1row = obase + wave * 32;
+  const long m0 = (long)blockIdx.x * a.rows_per_chunk;
+  const long m1 = min((long)a.M, m0 + a.rows_per_chunk);
+  if (m0 >= m1) return;
+  const uint32_t rows_bytes = (uint32_t)((long)a.M * H * 4), xn_bytes = (uint32_t)((long)a.M * OP * 4);
+  const PBuf bdz2 = make_pbuf(a.dz2[trunk], (int)(rows_bytes / 4)), bh1 = make_pbuf(a.h1[trunk], (int)(rows_bytes / 4));
+  const PBuf bdz1 = make_pbuf(a.dz1[trunk], (int)(rows_bytes / 4));
+  const PBuf bxn = make_pbuf(a.xn, (int)(xn_bytes / 4));
+  // this thread's share of a stage: of each 16 x 256 source rows 2 wave, 2 wave + 1 as two float4. A 16-lane
+  // group (one LDS cycle of a ds_write_b64) takes 32 columns of both rows: 2 x 64 adjacent bytes of the image,
+  // every bank once; waves < NXI also one float4 of Xn
+  const int srow = 2 * wave + ((lane >> 3) & 1), scol = 32 * (lane >> 4) + 4 * (lane & 7);  // second float4: + 128 columns
+  const int xe = wave * 256 + lane * 4, xrow = xe / OP, xcol = xe - xrow * OP;
+  const bool xw = wave < NXI;
+  const int wofs = dwso_off(srow, scol);                // + 4096: the second float4
+  const int xwofs = GE::oXN + 64 * xrow + 2 * xcol;
+  f4 pv[6], px = {0.f, 0.f, 0.f, 0.f};
+  // source s3 (0 DZ2, 1 H1, 2 DZ1, 3 Xn) of the stage at rows mb into its registers
+  auto load_src = [&](long mb, int s3) {
+    if (s3 < 3) {
+      const long row = mb + srow;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const uint32_t voff = row < m1 ? (uint32_t)((row * H + scol + 128 * i) * 4) : 0xFFFFFFF0u;
+        pv[2 * s3 + i] = __builtin_bit_cast(
+            f4, __builtin_amdgcn_raw_buffer_load_b128((s3 == 0 ? bdz2 : s3 == 1 ? bh1 : bdz1).r, voff, 0, PPO_DW_AUX));
+      }
+    } else {  // (the other waves: out of range, no memory access, zeros)
+      const long xr = mb + xrow;
+      const uint32_t voff = xw && xr < m1 ? (uint32_t)((xr * OP + xcol) * 4) : 0xFFFFFFF0u;
+      px = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(bxn.r, voff, 0, PPO_DW_AUX));
+    }
+  };
+  auto load = [&](long mb) {
+#pragma unroll
+    for (int s3 = 0; s3 < 4; ++s3) load_src(mb, s3);
+  };
+  // split + store source s3 (0 DZ2, 1 H1, 2 DZ1, 3 Xn) of the registers into image img
+  auto put = [&](unsigned char* img, int s3) {
+    if (s3 < 3) {
+      dwso_split_store<GE::PIECE>(img + s3 * GE::SRC + wofs, pv[2 * s3]);
+      dwso_split_store<GE::PIECE>(img + s3 * GE::SRC + wofs + 4096, pv[2 * s3 + 1]);
+    } else {  // branch-free: the waves without an Xn share store their zeros into the spill area behind the images
+      dwso_split_store<GE::XPIECE>(xw ? img + xwofs : ldsb + GE::total + 8 * lane, px);
+    }
+  };
+  // transposed-read addresses (bytes in a source's hi piece, column block 0): lane 4 q + p of 16-lane group g
+  // addresses row 8 (g >> 1) + 4 j + q, columns 16 (g & 1) + 4 p .. + 3; a column block C (multiple of 32)
+  // adds dwso_off(0, C)
+  const int rq = (lane >> 2) & 3, rc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int rofs0 = dwso_off(8 * hs + rq, rc), rofs1 = dwso_off(8 * hs + 4 + rq, rc);
+  const int xrofs = GE::oXN + 64 * (8 * hs + rq) + 2 * rc;  // rows + 4: + 256 bytes
+  f16v acc[TOW][TIW], acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    acc1[r] = 0.0f;
+#pragma unroll
+    for (int u = 0; u < TOW; ++u)
+#pragma unroll
+      for (int v = 0; v < TIW; ++v) acc[u][v][r] = 0.0f;
+  }
+  if constexpr (OP < 32) {  // Xn columns OP .. 31 of both images: zero, never written again
+    constexpr int NZ = 3 * GE::XPIECE / 4;  // dwords per image
+    for (int i = tid; i < 2 * NZ; i += 512)
+      *reinterpret_cast<unsigned*>(ldsb + (i >= NZ ? GE::IMG : 0) + GE::oXN + 4 * (i >= NZ ? i - NZ : i)) = 0u;
+    lds_barrier();
+  }
+  const int nst = (int)((m1 - m0 + KS - 1) / KS);
+#if PPO_DWSO_PRIO
+  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+#endif
+  // prologue: stage 0 into image 0, stage 1 into the registers. Stages past the last load zeros and are
+  // never read.
+  load(m0);
+#pragma unroll
+  for (int s3 = 0; s3 < 4; ++s3) put(ldsb, s3);
+  load(m0 + KS);
+  lds_barrier();
+  for (int sI = 0; sI < nst; ++sI) {
+    // image sI & 1 holds stage sI (barrier behind us), the registers stage sI + 1, whose pieces go into the
+    // other image between this stage's MFMAs: its last readers passed the barrier that ended stage sI - 1
+    const unsigned char* ib = ldsb + (sI & 1) * GE::IMG;
+    unsigned char* ob = ldsb + ((sI + 1) & 1) * GE::IMG;
+    if (w1_wave) {
+      const Split3 a1s = dwso_operand<GE::PIECE>(ib + 2 * GE::SRC + dwso_off(0, w1row) + rofs0,
+                                                 ib + 2 * GE::SRC + dwso_off(0, w1row) + rofs1);
+      const Split3 b1s = dwso_operand<GE::XPIECE>(ib + xrofs, ib + xrofs + 256);
+      acc1 = mfma_split<NP>(a1s, b1s, acc1);
+    }
+    Split3 as[TOW];
+#pragma unroll
+    for (int u = 0; u < TOW; ++u) {
+      const int c = dwso_off(0, obase + (wo * TOW + u) * 32);
+      as[u] = dwso_operand<GE::PIECE>(ib + c + rofs0, ib + c + rofs1);
+    }
+    const int cb = GE::SRC + dwso_off(0, wi * TIW * 32);  // (TIW = 4 column blocks: 512 bytes apart)
+    const long mb2 = m0 + (long)(sI + 2) * KS;  // the stage whose loads replace the registers just split
+#if PPO_DWSO_SGB
+    Split3 bs = dwso_operand<GE::PIECE>(ib + cb + rofs0, ib + cb + rofs1);
+#pragma unroll
+    for (int v = 0; v < TIW; ++v) {
+      // the H1 operand of block v + 1 is read, and a quarter of stage sI + 1 split and stored, between this
+      // block's MFMAs: per MFMA its share of the VALU and LDS instructions (fenced per block)
+      __builtin_amdgcn_sched_barrier(0);
+      Split3 bn = bs;
+      if (v + 1 < TIW) bn = dwso_operand<GE::PIECE>(ib + cb + 512 * (v + 1) + rofs0, ib + cb + 512 * (v + 1) + rofs1);
+#pragma unroll
+      for (int u = 0; u < TOW; ++u) acc[u][v] = mfma_split<NP>(as[u], bs, acc[u][v]);
+      put(ob, v);
+      bs = bn;
+      constexpr int NM = TOW * NP;
+#pragma unroll
+      for (int g = 0; g < NM; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                   // one MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, (52 + NM - 1) / NM, 0);  // its VALU
+        __builtin_amdgcn_sched_group_barrier(0x080, (12 + NM - 1) / NM, 0);  // its LDS reads / stores
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (PPO_DWSO_RELOAD) load_src(mb2, v);
+    }
+#else
+#pragma unroll
+    for (int v = 0; v < TIW; ++v) {
+      const Split3 bs = dwso_operand<GE::PIECE>(ib + cb + 512 * v + rofs0, ib + cb + 512 * v + rofs1);
+#pragma unroll
+      for (int u = 0; u < TOW; ++u) acc[u][v] = mfma_split<NP>(as[u], bs, acc[u][v]);
+      put(ob, v);
+      if (PPO_DWSO_RELOAD) load_src(mb2, v);
+    }
+#endif
+    if (!PPO_DWSO_RELOAD) load(mb2);
+    lds_barrier();
+  }
+  float* out = a.slab[trunk] + (size_t)blockIdx.x * a.slab_stride;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int orow = (r & 3) + 8 * (r >> 2) + 4 * hs;
+#pragma unroll
+    for (int u = 0; u < TOW; ++u)
+#pragma unroll
+      for (int v = 0; v < TIW; ++v)
+        dw_st(out + (size_t)(obase + (wo * TOW + u) * 32 + orow) * H + (wi * TIW + v) * 32 + l32, acc[u][v][r]);
+    if (w1_wave && l32 < OP) dw_st(out + (size_t)H * H + (size_t)(w1row + orow) * OP + l32, acc1[r]);
+  }
+}
+
+// =============================================================================================
 // k_colsum — dst[seg] = sum_{c < C} src[c * stride + seg]   (fixed order => deterministic)
 // =============================================================================================
 // The segments are cut into 64-float column tiles, numbered consecutively over all segments
@@ -2342,6 +2578,18 @@ static int launch_dwf_t(const DwArgs& a0, int nchunks, hipStream_t s) {
   a.hot = hot;
 #endif
   // the DMA kernels address their sources through 32-bit buffer descriptors (make_pbuf: int floats)
+  if (a.bx && a.split_once && !a.h1_recompute && (long)a.M * H < (1L << 29)) {
+    auto k = a.bx == 9 ? k_dwf_so<H, OP, NSL, 9> : a.bx == 8 ? k_dwf_so<H, OP, NSL, 8> : k_dwf_so<H, OP, NSL, 6>;
+    constexpr size_t lds = DwsoGeo<OP>::lds;
+    static bool attr[3] = {false, false, false};
+    const int ai = a.bx == 9 ? 2 : a.bx == 8 ? 1 : 0;
+    if (!attr[ai]) {
+      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
+      attr[ai] = true;
+    }
+    hipLaunchKernelGGL(k, dim3(nchunks, 2, NSL), dim3(512), lds, s, a);
+    return 0;
+  }
   if (a.bx && (long)a.M * H < (1L << 29)) {
     const bool rc = a.h1_recompute != 0;
     auto k = rc ? (a.bx == 9 ? k_dwf_bx<H, OP, NSL, 9, true> : a.bx == 8 ? k_dwf_bx<H, OP, NSL, 8, true>

@@ -73,6 +73,16 @@ PPO_DEV_HOST inline long bx_index(int r, int c, int ncols, int p) {
   return ((((long)(r >> 4) * (ncols >> 5) + (c >> 5)) * 3 + p) * 64 + lane) * 8 + e;
 }
 PPO_DEV_HOST inline long bx_size(int H) { return 3L * H * H; }  // floats: W2 | W2^T pieces
+// Piece image of one 16-row x 256-column stage source of the split-once dW kernel (k_dwf_so): byte offset of
+// the four bf16 of row `row`, columns col .. col + 3 (col a multiple of 4) in the 8 KB image of one piece.
+// 8-row x 32-column subtiles of 512 B, the 16-byte chunks of a subtile row XORed with (row >> 2) & 3
+// (cdna_hip_programming.md T10, image (a), two 128-column tiles side by side): the four rows x 32 columns
+// that a 32-lane half takes in one ds_read_b64_tr_b16 are 256 contiguous bytes, each 8-byte slot once.
+// The splitting threads store through this map and the transposed reads address through it.
+PPO_DEV_HOST inline constexpr int dwso_off(int row, int col) {
+  return 4096 * (col >> 7) + 2048 * (row >> 3) + 512 * ((col >> 5) & 3) + 64 * (row & 7) +
+         16 * (((col >> 3) & 3) ^ ((row >> 2) & 3)) + 8 * ((col >> 2) & 1);
+}
 // the 64-wide agent (k_upd2's split-bf16 layer 1): the pieces of W1 (H x OP) instead, same layout
 PPO_DEV_HOST inline long bx_w1_size(int H, int OP) { return 3L * H * OP / 2; }
 // floats of a trunk's piece region (after its fp32 swizzled copies)
@@ -136,6 +146,7 @@ struct DwArgs {
                       // split-K partials, for small minibatches (dw_slices)
   int dma;            // k_dwf: 1 stages the rows by LDS DMA, three buffers (k_dwf_dma), bitwise k_dwf
   int bx;             // k_dwf: 8 / 9 runs the products as exact bf16 piece products (k_dwf_bx); 0 fp32 MFMA
+  int split_once;     // k_dwf_bx without h1_recompute: 1 runs its split-once form k_dwf_so (bitwise the same dW)
   int hot;            // diagnostic build only (PPO_DW_HOT): every stage re-reads the chunk's first rows (L2-hot)
   // h1_recompute (k_dwf_bx, LayerNorm agent): H1 is not read; each 16-row stage recomputes it from the Xn
   // rows it stages anyway, k_upd's layer-1 chain (W1 swizzled copy, bias init, 16x16x4 fp32 MFMAs in the

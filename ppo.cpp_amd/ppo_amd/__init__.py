@@ -188,6 +188,7 @@ SYMBOLS = [
     ("ppo_comm_info", _I, [_VP, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     ("ppo_get_device", _I, [_VP, C.POINTER(_I), C.c_char_p, _I]),
     ("ppo_kernel_info", _I, [_VP, C.c_char_p, _I]),
+    ("ppo_dw_image_offset", _I, [_I, _I]),
     ("ppo_set_device", _I, [_I]),
     ("ppo_device_count", _I, [C.POINTER(_I)]),
     ("ppo_dev_malloc", _I, [C.POINTER(_VP), _SZ]),
