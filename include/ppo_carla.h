@@ -33,6 +33,14 @@
  * linear.{0,1,3,4}, ..., value_head.{0,1,3,4,6}). Everything above — ppo_carla_layout,
  * ppo_carla_create(_ex), the default agent's kernels and results — is unchanged by them.
  * "roach_ln2" and use_positional_encoding are not built.
+ *
+ * The training iteration around the agent (ac_ppo_carla.cpp:284-621) is a second handle,
+ * ppo_carla_rollout_t, created from an agent: [T, E] storage of the dict observations on the device,
+ * act-and-store, GAE over a full or preempted collection, the per-epoch permutation, the row gather of
+ * each minibatch (k_carla_gather) and update_epochs x num_minibatches calls of ppo_carla_update without
+ * a host synchronisation in between. See "rollout storage, GAE and the epoch loop" below for its three
+ * rules: calls on one object are serial, every size is 64-bit, and a partial collection bootstraps
+ * from the stored step. The agent's struct, kernels, defaults and results are unchanged by it.
  */
 #ifndef PPO_CARLA_H
 #define PPO_CARLA_H
@@ -347,6 +355,101 @@ int ppo_carla_debug_ln_backward(int n, int F, const float* z, long in_stride, co
 int ppo_carla_comm_init(ppo_carla_t* c, const char* id, int rank, int world);
 /* ac_ppo_carla.cpp:241-244: every parameter from `root` to all ranks */
 int ppo_carla_comm_broadcast_params(ppo_carla_t* c, int root);
+/* in-place all-reduce (sum, or average) of buf[0..n) (device pointer) over the agent's communicator on
+ * the agent's stream, then a stream synchronisation; no communicator: the identity (:439-441, :346) */
+int ppo_carla_comm_allreduce(ppo_carla_t* c, float* buf, long n, int average);
+
+/* ---- rollout storage, GAE and the epoch loop (ac_ppo_carla.cpp:284-621) -------------------------
+ * A rollout object sits beside an agent and holds one collection of T steps x E envs on the agent's
+ * device: bev uint8 [T, E, C, IH, IW], measurements [T, E, NM], value_measurements [T, E, NV],
+ * actions [T, E, A] and logprobs / rewards / dones / values / advantages / returns [T, E], all fp32
+ * but the bev (:285-295). It computes through ppo_carla_forward and ppo_carla_update only, so what
+ * those document (sampling contract, loss, data parallelism of an attached communicator) holds here.
+ *
+ * Serial calls. The agent's activation buffers are shared by every forward and update, and the
+ * object's minibatch staging buffers by every train call: calls on one rollout object, and on its
+ * agent while the object is in use, must be made one after the other (from any one thread at a
+ * time), each on the same stream (NULL = the agent's own). The per-thread concurrency of
+ * ppo_rollout_act (one thread and stream per env range) is NOT offered: ranges of one step are
+ * passed in successive calls. The agent must outlive the object.
+ *
+ * 64-bit sizing. One bev row is C * IH * IW bytes (552 960 for 15 x 192 x 192): 7 767 rows pass
+ * 2^32 bytes, and a collection of 65 536 rows is 36 GB. Every size, row offset and byte index of
+ * the storage, the staging buffers and the gather kernel is a 64-bit integer; only the row
+ * indices of a permutation are int32 (T * E < 2^31 is checked).
+ *
+ * Partial collections (DD-PPO preemption, :399-436, :490-504, :531-538). num_steps_collected < T
+ * says that every env stored the steps [0, num_steps_collected) and, before it stopped, also
+ * executed rollout_act for step num_steps_collected (the preemption test runs after the step, so
+ * the stored values / dones of that step exist). GAE then bootstraps its last step from the STORED
+ * step num_steps_collected — values[t + 1], dones[t + 1] whenever t != T - 1, the reference's
+ * recurrence and what ppo_compute_gae documents — and the next observation's value is computed
+ * but not read. Training permutes the Bc = num_steps_collected * E collected rows and repeats the
+ * permutation up to the full batch B = T * E, truncated (b_inds.repeat(ceil(B / Bc))[:B]). */
+typedef struct ppo_carla_rollout_config {
+  int num_steps, num_envs;           /* T, E: envs on this device (num_envs_per_proc) */
+  int update_epochs, num_minibatches;
+  float gamma, gae_lambda;           /* 0.99, 0.95 */
+  uint64_t seed;                     /* permutation key (seed, rank, epoch counter), as ppo_hip.h */
+  int rank;
+} ppo_carla_rollout_config;
+
+typedef struct ppo_carla_rollout ppo_carla_rollout_t;
+
+/* ppo_carla_rollout_buffer's `which` */
+enum {
+  PPO_CARLA_BUF_BEV = 0, PPO_CARLA_BUF_MEAS, PPO_CARLA_BUF_VMEAS, PPO_CARLA_BUF_ACTIONS, PPO_CARLA_BUF_LOGP,
+  PPO_CARLA_BUF_REWARDS, PPO_CARLA_BUF_DONES, PPO_CARLA_BUF_VALUES, PPO_CARLA_BUF_ADV, PPO_CARLA_BUF_RETURNS,
+  PPO_CARLA_BUF_NEXT_VALUE,          /* [E]: the bootstrap value of the last ppo_carla_rollout_gae */
+  PPO_CARLA_BUF_COUNT
+};
+
+/* Refused before any HIP call: a NULL agent / config / out, non-positive sizes, T * E not divisible
+ * by num_minibatches (or 2^31 and more), an agent whose max_batch is below
+ * max(E, T * E / num_minibatches). The storage starts zeroed. */
+int ppo_carla_rollout_create(ppo_carla_t* agent, const ppo_carla_rollout_config* cfg, ppo_carla_rollout_t** out);
+int ppo_carla_rollout_destroy(ppo_carla_rollout_t* r);
+/* :365-379 for envs [env_begin, env_end) at `step`: stores the observation rows and next_done, runs
+ * ppo_carla_forward(SAMPLE, env_base = env_begin, step_id = iteration * T + step) on them and stores
+ * action, log-prob and value; action_out [env_end - env_begin, A] (may be NULL) receives the actions.
+ * Device pointers that address row env_begin: bev [n, C, IH, IW], meas [n, NM], vmeas [n, NV],
+ * next_done [n]. */
+int ppo_carla_rollout_act(ppo_carla_rollout_t* r, int step, int env_begin, int env_end, const uint8_t* bev,
+                          const float* meas, const float* vmeas, const float* next_done, float* action_out,
+                          void* stream);
+/* :385: rewards[step, env_begin .. env_end) = reward[0 .. env_end - env_begin) (device pointer) */
+int ppo_carla_rollout_reward(ppo_carla_rollout_t* r, int step, int env_begin, int env_end, const float* reward,
+                             void* stream);
+/* :484-504: the bootstrap value from one forward on the next observation [E, ...] (value output only),
+ * advantages over steps [0, num_steps_collected), returns = advantages + values. */
+int ppo_carla_rollout_gae(ppo_carla_rollout_t* r, const uint8_t* next_bev, const float* next_meas,
+                          const float* next_vmeas, const float* next_done, int num_steps_collected, void* stream);
+/* :531-621: update_epochs x num_minibatches optimizer steps on the agent's stream. Per epoch the
+ * permutation of make_perm_key(seed, rank, iteration * update_epochs + epoch, Bc) over the collected
+ * rows, repeated and truncated to B = T * E; perms_dev int32 [update_epochs][B] (device, may be NULL)
+ * replaces it. Each minibatch's rows are gathered into contiguous staging buffers (k_carla_gather)
+ * and passed to ppo_carla_update. `last` (may be NULL) receives the last minibatch's statistics,
+ * rank-averaged as ppo_carla_update's; mean_clipfrac (may be NULL) the mean clipfrac over all
+ * minibatches (:637, rank-averaged, :651). There is no host synchronisation between minibatches, and
+ * none at all when both are NULL. Advances the iteration counter. */
+int ppo_carla_rollout_train(ppo_carla_rollout_t* r, const ppo_carla_train_config* tc, float lr,
+                            int num_steps_collected, const int32_t* perms_dev, ppo_carla_update_stats* last,
+                            float* mean_clipfrac);
+/* device pointer of a storage array (PPO_CARLA_BUF_*) */
+int ppo_carla_rollout_buffer(ppo_carla_rollout_t* r, int which, void** dev_ptr);
+/* host copy of the indices the last ppo_carla_rollout_train used: n = update_epochs * T * E */
+int ppo_carla_rollout_last_perms(ppo_carla_rollout_t* r, int32_t* host, long n);
+long ppo_carla_rollout_iteration(const ppo_carla_rollout_t* r);
+int ppo_carla_rollout_set_iteration(ppo_carla_rollout_t* r, long iteration);
+
+/* ---- test hooks: the rollout object's gather launches on caller arrays (device pointers) ---------
+ * k_carla_gather: dst[i, 0..row_bytes) = src[idx[i], 0..row_bytes) for i < n; rows are packed
+ * (stride row_bytes), neither base pointer nor row_bytes need be a multiple of 16. n = 0 is a no-op.
+ * k_carla_gather_f32: the same for nseg <= 8 fp32 arrays in one launch, rows of width[k] floats;
+ * src / dst / width are HOST arrays of nseg entries (the pointers in them device pointers). */
+int ppo_carla_debug_gather(long n, long row_bytes, const void* src, const int32_t* idx, void* dst, void* stream);
+int ppo_carla_debug_gather_f32(long n, int nseg, const float* const* src, const int* width, const int32_t* idx,
+                               float* const* dst, void* stream);
 
 #ifdef __cplusplus
 }

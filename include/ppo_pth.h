@@ -54,6 +54,12 @@ int ppo_carla_pth_load(const ppo_carla_layout* L, const char* path, float* param
  * written for another arch fails and names the first parameter it lacks. */
 int ppo_carla_pth_save2(const ppo_carla_layout2* L, const float* params, const char* path);
 int ppo_carla_pth_load2(const ppo_carla_layout2* L, const char* path, float* params, long n);
+/* the CaRL trainer's optimizer_*.pth (ac_ppo_carla.cpp:62-73 save_state, :246-251): ppo_pth_save_adam /
+ * ppo_pth_load_adam over the tensors of a ppo_carla_layout2 (action_space_high / _low carry no state) */
+int ppo_carla_pth_save_adam2(const ppo_carla_layout2* L, const float* m, const float* v, long step, double lr,
+                             double eps, const char* path);
+int ppo_carla_pth_load_adam2(const ppo_carla_layout2* L, const char* path, float* m, float* v, long n, long* step,
+                             double* lr_out, double* eps_out);
 
 #ifdef __cplusplus
 }

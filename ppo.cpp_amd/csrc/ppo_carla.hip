@@ -26,6 +26,7 @@
 #include "../../include/ppo_carla.h"
 #include "../../include/ppo_hip.h"
 #include "ppo_agent.hpp"
+#include "ppo_carla_internal.hpp"
 #include "ppo_kernels.hpp"
 
 namespace {
@@ -4024,6 +4025,15 @@ extern "C" int ppo_carla_comm_broadcast_params(ppo_carla_t* c, int root) {
   return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : ppo_fail("ppo_carla_comm_broadcast_params: sync failed", -2);
 }
 
+extern "C" int ppo_carla_comm_allreduce(ppo_carla_t* c, float* buf, long n, int average) {
+  if (!c || !buf || n < 0) return ppo_fail("ppo_carla_comm_allreduce: bad argument", -1);
+  if (!c->comm || n == 0) return 0;
+  if (hipSetDevice(c->device) != hipSuccess) return ppo_fail("ppo_carla_comm_allreduce: hipSetDevice failed", -2);
+  if (ncclAllReduce(buf, buf, (size_t)n, ncclFloat, average ? ncclAvg : ncclSum, c->comm, c->stream) != ncclSuccess)
+    return ppo_fail("ppo_carla_comm_allreduce: ncclAllReduce failed", -3);
+  return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : ppo_fail("ppo_carla_comm_allreduce: sync failed", -2);
+}
+
 // ------------------------------------------------------------------------------------------
 // test hooks: the agent's LayerNorm launches on caller arrays (ppo_carla.h)
 // ------------------------------------------------------------------------------------------
@@ -4059,4 +4069,21 @@ extern "C" int ppo_carla_debug_ln_backward(int n, int F, const float* z, long in
   const bool ok = fit == 0 && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   (void)hipFree(part);
   return ok ? 0 : ppo_fail("ppo_carla_debug_ln_backward: launch failed", -2);
+}
+
+// ------------------------------------------------------------------------------------------
+// internal entry points of the rollout object (ppo_carla_internal.hpp, ppo_carla_rollout.hip)
+// ------------------------------------------------------------------------------------------
+int carla_agent_info(const ppo_carla_t* c, CarlaAgentInfo* out) {
+  if (!c || !out) return ppo_fail("carla_agent_info: null argument", -1);
+  *out = CarlaAgentInfo{c->device, c->cfg.max_batch, c->stream};
+  return 0;
+}
+
+int carla_stats_to_slot(ppo_carla_t* c, float* slot, hipStream_t s) {
+  if (!c || !slot) return ppo_fail("carla_stats_to_slot: null argument", -1);
+  if (!c->train_ready) return ppo_fail("carla_stats_to_slot: no update has run", -1);
+  if (hipMemcpyAsync(slot, c->small + 64, kCarlaStatSlot * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return ppo_fail("carla_stats_to_slot: copy failed", -2);
+  return 0;
 }

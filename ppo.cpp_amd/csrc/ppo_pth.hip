@@ -302,3 +302,34 @@ extern "C" int ppo_carla_pth_load2(const ppo_carla_layout2* L, const char* path,
     return 0;
   });
 }
+
+// torch::save / torch::load of the CaRL trainer's Adam (ac_ppo_carla.cpp:62-73, :246-251)
+extern "C" int ppo_carla_pth_save_adam2(const ppo_carla_layout2* L, const float* m, const float* v, long step,
+                                        double lr, double eps, const char* path) {
+  if (!L || !m || !v || !path) return ppo_fail("ppo_carla_pth_save_adam2: null argument", -1);
+  if (step < 0) return ppo_fail("ppo_carla_pth_save_adam2: negative step", -1);
+  return guarded([&] {
+    const pth::Spec s = carla_spec2(*L);
+    if (!covers(s)) return ppo_fail("ppo_carla_pth_save_adam2: layout does not match the agent structure", -1);
+    pth::AdamOptions o;
+    o.lr = lr;
+    o.eps = eps;
+    pth::save_adam(path, s, m, v, step, o);
+    return 0;
+  });
+}
+
+extern "C" int ppo_carla_pth_load_adam2(const ppo_carla_layout2* L, const char* path, float* m, float* v, long n,
+                                        long* step, double* lr_out, double* eps_out) {
+  if (!L || !m || !v || !path || !step) return ppo_fail("ppo_carla_pth_load_adam2: null argument", -1);
+  if (n != L->P) return ppo_fail("ppo_carla_pth_load_adam2: n != layout P", -1);
+  return guarded([&] {
+    const pth::Spec s = carla_spec2(*L);
+    if (!covers(s)) return ppo_fail("ppo_carla_pth_load_adam2: layout does not match the agent structure", -1);
+    pth::AdamOptions o;
+    *step = pth::load_adam(path, s, m, v, &o);
+    if (lr_out) *lr_out = o.lr;
+    if (eps_out) *eps_out = o.eps;
+    return 0;
+  });
+}

@@ -143,6 +143,17 @@ class CarlaConfig(C.Structure):  # ppo_carla_config; defaults = carla_config.h
 
 PPO_CARLA_SAMPLE, PPO_CARLA_MEAN, PPO_CARLA_GIVEN, PPO_CARLA_ROACH = range(4)
 
+
+class CarlaRolloutConfig(C.Structure):  # ppo_carla_rollout_config
+    _fields_ = [("num_steps", C.c_int), ("num_envs", C.c_int), ("update_epochs", C.c_int),
+                ("num_minibatches", C.c_int), ("gamma", C.c_float), ("gae_lambda", C.c_float),
+                ("seed", C.c_uint64), ("rank", C.c_int)]
+
+
+# ppo_carla_rollout_buffer's `which` (PPO_CARLA_BUF_*)
+CARLA_BUFFERS = ("bev", "meas", "vmeas", "actions", "logp", "rewards", "dones", "values", "adv", "returns",
+                 "next_value")
+
 _LIB = None
 
 # (name, restype, argtypes) of every entry point declared in include/ppo_hip.h / ppo_synth_env.h /
@@ -249,6 +260,23 @@ SYMBOLS = [
     ("ppo_carla_pth_load2", _I, [C.POINTER(CarlaLayout2), C.c_char_p, _FP, _L]),
     ("ppo_carla_debug_ln_forward", _I, [_I, _I, _FP, _L, _FP, _FP, _FP, _L, _FP, _VP]),
     ("ppo_carla_debug_ln_backward", _I, [_I, _I, _FP, _L, _FP, _FP, _FP, _L, _FP, _FP, _FP, _FP, _VP]),
+    ("ppo_carla_comm_allreduce", _I, [_VP, _FP, _L, _I]),
+    ("ppo_carla_pth_save_adam2", _I, [C.POINTER(CarlaLayout2), _FP, _FP, _L, C.c_double, C.c_double, C.c_char_p]),
+    ("ppo_carla_pth_load_adam2", _I, [C.POINTER(CarlaLayout2), C.c_char_p, _FP, _FP, _L, C.POINTER(_L),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("ppo_carla_rollout_create", _I, [_VP, C.POINTER(CarlaRolloutConfig), C.POINTER(_VP)]),
+    ("ppo_carla_rollout_destroy", _I, [_VP]),
+    ("ppo_carla_rollout_act", _I, [_VP, _I, _I, _I, _VP, _FP, _FP, _FP, _FP, _VP]),
+    ("ppo_carla_rollout_reward", _I, [_VP, _I, _I, _I, _FP, _VP]),
+    ("ppo_carla_rollout_gae", _I, [_VP, _VP, _FP, _FP, _FP, _I, _VP]),
+    ("ppo_carla_rollout_train", _I, [_VP, C.POINTER(CarlaTrainConfig), _F, _I, _VP, C.POINTER(CarlaUpdateStats),
+                                     C.POINTER(_F)]),
+    ("ppo_carla_rollout_buffer", _I, [_VP, _I, C.POINTER(_VP)]),
+    ("ppo_carla_rollout_last_perms", _I, [_VP, _VP, _L]),
+    ("ppo_carla_rollout_iteration", _L, [_VP]),
+    ("ppo_carla_rollout_set_iteration", _I, [_VP, _L]),
+    ("ppo_carla_debug_gather", _I, [_L, _L, _VP, _VP, _VP, _VP]),
+    ("ppo_carla_debug_gather_f32", _I, [_L, _I, C.POINTER(_VP), C.POINTER(_I), _VP, C.POINTER(_VP), _VP]),
 ]
 
 
@@ -366,6 +394,22 @@ def load_carla_pth2(layout: CarlaLayout2, path):
     out = np.empty(layout.P, np.float32)
     check(lib().ppo_carla_pth_load2(C.byref(layout), os.fsencode(path), out.ctypes.data, layout.P))
     return out
+
+
+def save_carla_adam_pth2(layout: CarlaLayout2, m, v, step, lr, eps, path):
+    """torch::save(optimizer, path) of the CaRL trainer's Adam (ac_ppo_carla.cpp:62-73)"""
+    m, v = _f32(m, layout.P), _f32(v, layout.P)
+    check(lib().ppo_carla_pth_save_adam2(C.byref(layout), m.ctypes.data, v.ctypes.data, int(step), float(lr),
+                                         float(eps), os.fsencode(path)))
+
+
+def load_carla_adam_pth2(layout: CarlaLayout2, path):
+    """torch::load(optimizer, path) -> (exp_avg, exp_avg_sq, step, lr, eps)"""
+    m, v = np.empty(layout.P, np.float32), np.empty(layout.P, np.float32)
+    step, lr, eps = C.c_long(0), C.c_double(0), C.c_double(0)
+    check(lib().ppo_carla_pth_load_adam2(C.byref(layout), os.fsencode(path), m.ctypes.data, v.ctypes.data, layout.P,
+                                         C.byref(step), C.byref(lr), C.byref(eps)))
+    return m, v, step.value, lr.value, eps.value
 
 
 def obs_norm(env_id):
@@ -804,6 +848,155 @@ class CarlaAgent:
 
     def comm_broadcast_params(self, root=0):
         check(lib().ppo_carla_comm_broadcast_params(self._h, root))
+
+
+class CarlaRollout:
+    """Rollout storage, GAE and the epoch loop of the CaRL trainer (ac_ppo_carla.cpp:284-621) beside a
+    CarlaAgent: ppo_carla_rollout_* of include/ppo_carla.h. Calls are serial (the agent's activation
+    buffers are shared); every array argument is a DeviceArray."""
+
+    def __init__(self, agent: CarlaAgent, num_steps, num_envs, update_epochs=3, num_minibatches=4, gamma=0.99,
+                 gae_lambda=0.95, seed=1, rank=0):
+        self.agent = agent  # keeps the agent alive: it must outlive the handle
+        self.cfg = CarlaRolloutConfig(num_steps, num_envs, update_epochs, num_minibatches, gamma, gae_lambda, seed,
+                                      rank)
+        self._h = C.c_void_p()
+        check(lib().ppo_carla_rollout_create(agent._h, C.byref(self.cfg), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().ppo_carla_rollout_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def act(self, step, e0, e1, bev: DeviceArray, meas: DeviceArray, vmeas: DeviceArray, next_done: DeviceArray,
+            action_out: DeviceArray | None = None):
+        """the arrays address row e0 (n = e1 - e0 rows)"""
+        check(lib().ppo_carla_rollout_act(self._h, step, e0, e1, bev.ptr, meas.ptr, vmeas.ptr, next_done.ptr,
+                                          action_out.ptr if action_out is not None else None, None))
+
+    def reward(self, step, e0, e1, reward: DeviceArray):
+        check(lib().ppo_carla_rollout_reward(self._h, step, e0, e1, reward.ptr, None))
+
+    def gae(self, next_bev: DeviceArray, next_meas: DeviceArray, next_vmeas: DeviceArray, next_done: DeviceArray,
+            num_steps_collected=None):
+        check(lib().ppo_carla_rollout_gae(self._h, next_bev.ptr, next_meas.ptr, next_vmeas.ptr, next_done.ptr,
+                                          self.cfg.num_steps if num_steps_collected is None else num_steps_collected,
+                                          None))
+
+    def train(self, lr=3e-4, num_steps_collected=None, perms: DeviceArray | None = None, want_stats=True,
+              clip_coef=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, adam_eps=1e-5, norm_adv=True,
+              clip_vloss=True):
+        """update_epochs x num_minibatches optimizer steps; with want_stats the last minibatch's statistics
+        plus "mean_clipfrac" (no host synchronisation without)."""
+        tc = CarlaTrainConfig(clip_coef, ent_coef, vf_coef, max_grad_norm, adam_eps, int(norm_adv), int(clip_vloss))
+        st, mc = CarlaUpdateStats(), C.c_float(0)
+        check(lib().ppo_carla_rollout_train(self._h, C.byref(tc), lr,
+                                            self.cfg.num_steps if num_steps_collected is None else num_steps_collected,
+                                            perms.ptr if perms is not None else None,
+                                            C.byref(st) if want_stats else None, C.byref(mc) if want_stats else None))
+        if not want_stats:
+            return None
+        d = st.as_dict()
+        d["mean_clipfrac"] = mc.value
+        return d
+
+    def buffer(self, name) -> DeviceArray:
+        """the storage array `name` (CARLA_BUFFERS) as a DeviceArray view"""
+        L, T, E = self.agent.layout2, self.cfg.num_steps, self.cfg.num_envs
+        shape = {"bev": (T, E, L.C, L.IH, L.IW), "meas": (T, E, L.NM), "vmeas": (T, E, L.NV), "actions": (T, E, L.A),
+                 "next_value": (E,)}.get(name, (T, E))
+        p = C.c_void_p()
+        check(lib().ppo_carla_rollout_buffer(self._h, CARLA_BUFFERS.index(name), C.byref(p)))
+        return DeviceArray.wrap(p.value, shape, np.uint8 if name == "bev" else np.float32)
+
+    def last_perms(self):
+        out = np.empty((self.cfg.update_epochs, self.cfg.num_steps * self.cfg.num_envs), np.int32)
+        check(lib().ppo_carla_rollout_last_perms(self._h, out.ctypes.data, out.size))
+        return out
+
+    @property
+    def iteration(self):
+        return lib().ppo_carla_rollout_iteration(self._h)
+
+    def set_iteration(self, it):
+        check(lib().ppo_carla_rollout_set_iteration(self._h, int(it)))
+
+
+class CarlaTrainer:
+    """One iteration of the reference's CaRL loop (ac_ppo_carla.cpp:332-621) against caller-supplied
+    observations, mirroring Trainer: lr anneal -> T x (act, env step) -> GAE -> train. `env_step(actions)`
+    takes the [E, A] float32 actions and returns host arrays (bev uint8 [E, C, H, W], meas [E, NM],
+    vmeas [E, NV], reward [E], done [E]); `reset_obs` is the (bev, meas, vmeas) of the reset."""
+
+    def __init__(self, agent: CarlaAgent, env_step, reset_obs, num_steps, num_envs, num_iterations, update_epochs=3,
+                 num_minibatches=4, learning_rate=3e-4, lr_schedule="linear", gamma=0.99, gae_lambda=0.95, seed=1,
+                 rank=0, **train_kwargs):
+        self.agent, self.env_step = agent, env_step
+        self.rollout = CarlaRollout(agent, num_steps, num_envs, update_epochs, num_minibatches, gamma, gae_lambda,
+                                    seed, rank)
+        self.T, self.E = num_steps, num_envs
+        self.learning_rate, self.lr_schedule, self.num_iterations = learning_rate, lr_schedule, max(1, num_iterations)
+        self.train_kwargs = train_kwargs
+        bev, meas, vmeas = reset_obs
+        self.next_bev = DeviceArray.from_numpy(bev, np.uint8)
+        self.next_meas = DeviceArray.from_numpy(meas, np.float32)
+        self.next_vmeas = DeviceArray.from_numpy(vmeas, np.float32)
+        self.next_done = DeviceArray.from_numpy(np.zeros(num_envs, np.float32))
+        self.actions = DeviceArray((num_envs, agent.layout2.A))
+        self.reward = DeviceArray(num_envs)
+        self.iteration = 0
+        self.global_step = 0
+        self.last_stats = None
+
+    def lr_now(self):
+        if self.lr_schedule != "linear":
+            return self.learning_rate
+        frac = np.float32(1.0) - np.float32(self.iteration) / np.float32(self.num_iterations)
+        return float(np.float32(frac * np.float32(self.learning_rate)))
+
+    def iterate(self, want_stats=False):
+        lr = self.lr_now()
+        for step in range(self.T):
+            self.rollout.act(step, 0, self.E, self.next_bev, self.next_meas, self.next_vmeas, self.next_done,
+                             self.actions)
+            bev, meas, vmeas, reward, done = self.env_step(self.actions.numpy())
+            self.reward.upload(reward)
+            self.rollout.reward(step, 0, self.E, self.reward)
+            self.next_bev.upload(bev)
+            self.next_meas.upload(meas)
+            self.next_vmeas.upload(vmeas)
+            self.next_done.upload(done)
+        self.rollout.gae(self.next_bev, self.next_meas, self.next_vmeas, self.next_done)
+        st = self.rollout.train(lr, want_stats=want_stats, **self.train_kwargs)
+        self.iteration += 1
+        self.global_step += self.T * self.E
+        self.last_stats = st
+        return st
+
+    def close(self):
+        self.rollout.close()
+
+
+def carla_gather(src: "DeviceArray", idx: "DeviceArray", dst: "DeviceArray", n, row_bytes, src_offset=0,
+                 dst_offset=0):
+    """ppo_carla_debug_gather: dst[i, :] = src[idx[i], :] for n packed rows of row_bytes bytes; the byte
+    offsets move the base pointers (unaligned rows)."""
+    check(lib().ppo_carla_debug_gather(n, row_bytes, src.ptr + src_offset, idx.ptr, dst.ptr + dst_offset, None))
+
+
+def carla_gather_f32(srcs, idx: "DeviceArray", dsts, n, widths):
+    """ppo_carla_debug_gather_f32: the fp32 side arrays of a minibatch, one launch for all of them"""
+    k = len(srcs)
+    sp = (C.c_void_p * k)(*[s.ptr for s in srcs])
+    dp = (C.c_void_p * k)(*[d.ptr for d in dsts])
+    w = (C.c_int * k)(*widths)
+    check(lib().ppo_carla_debug_gather_f32(n, k, sp, w, idx.ptr, dp, None))
 
 
 def carla_ln_forward(z: "DeviceArray", gamma: "DeviceArray", beta: "DeviceArray", n, F, in_stride=None,
