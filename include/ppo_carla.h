@@ -41,6 +41,9 @@
  * a host synchronisation in between. See "rollout storage, GAE and the epoch loop" below for its three
  * rules: calls on one object are serial, every size is 64-bit, and a partial collection bootstraps
  * from the stored step. The agent's struct, kernels, defaults and results are unchanged by it.
+ *
+ * Concurrent collection (:355-417, one host thread, stream and batch-1 forward per env) is a third
+ * handle, ppo_carla_lane_t, created from a rollout object: see "act lanes" below.
  */
 #ifndef PPO_CARLA_H
 #define PPO_CARLA_H
@@ -370,8 +373,10 @@ int ppo_carla_comm_allreduce(ppo_carla_t* c, float* buf, long n, int average);
  * object's minibatch staging buffers by every train call: calls on one rollout object, and on its
  * agent while the object is in use, must be made one after the other (from any one thread at a
  * time), each on the same stream (NULL = the agent's own). The per-thread concurrency of
- * ppo_rollout_act (one thread and stream per env range) is NOT offered: ranges of one step are
- * passed in successive calls. The agent must outlive the object.
+ * ppo_rollout_act (one thread and stream per env range) is NOT offered by these calls: ranges of one
+ * step are passed in successive calls. It is what act lanes are for (below: ppo_carla_lane_t, one host
+ * thread, one stream and one private set of activation buffers per env). The agent must outlive the
+ * object.
  *
  * 64-bit sizing. One bev row is C * IH * IW bytes (552 960 for 15 x 192 x 192): 7 767 rows pass
  * 2^32 bytes, and a collection of 65 536 rows is 36 GB. Every size, row offset and byte index of
@@ -441,6 +446,61 @@ int ppo_carla_rollout_buffer(ppo_carla_rollout_t* r, int which, void** dev_ptr);
 int ppo_carla_rollout_last_perms(ppo_carla_rollout_t* r, int32_t* host, long n);
 long ppo_carla_rollout_iteration(const ppo_carla_rollout_t* r);
 int ppo_carla_rollout_set_iteration(ppo_carla_rollout_t* r, long iteration);
+
+/* ---- act lanes: concurrent collection (ac_ppo_carla.cpp:355-417) -----------------------------------
+ * The reference collects with one host thread, one stream and one batch-1 forward per env, so that E
+ * simulators tick at the same time. A lane is that thread's handle: created from a rollout object, it
+ * owns a stream, a private one-row copy of every buffer a forward writes (conv outputs, MLP
+ * activations, split-K partials, the packed conv1 weight table, the LayerNorm z / stat buffers, the
+ * cooperative tail's barrier counter) and a pinned host buffer for one observation and one action.
+ * Parameters stay shared: collection only reads them.
+ *
+ * Threads. Lanes of one rollout object may be used from different threads at the same time; one lane is
+ * used by one thread at a time. Every lane call selects the agent's device for the calling thread;
+ * ppo_last_error is thread-local. Two lanes must not act for the same (step, env) of one collection.
+ *
+ * Ordering is kept by events, not by the caller: ppo_carla_rollout_gae and _train make their stream wait
+ * for the last queued work of every lane (a ppo_carla_lane_reward still in flight included), and a
+ * lane's next act waits for the last ppo_carla_rollout_gae / _train of its object and for the agent's
+ * last ppo_carla_update, ppo_carla_load_params or ppo_carla_comm_broadcast_params.
+ *
+ * What stays forbidden: ppo_carla_update, ppo_carla_load_params, ppo_carla_comm_broadcast_params,
+ * ppo_carla_rollout_gae / _train / _set_iteration / _destroy or the creation and destruction of lanes
+ * while a lane call of that object is inside the library (join the collecting threads first; what a
+ * returned call left queued is covered by the events). A lane call that finds such a call inside the
+ * library, or the reverse, is refused where the library can tell (-1, "... while ..."): rollout_gae,
+ * rollout_train, lane_create and lane_destroy check the object's count of lane calls in progress, and a
+ * lane call checks that none of those four is in progress. The lanes must be destroyed before their
+ * rollout object. */
+#define PPO_CARLA_MAX_LANES 64
+
+typedef struct ppo_carla_lane ppo_carla_lane_t;
+
+/* Refused before any HIP call: NULL arguments, a 65th lane of one rollout object. */
+int ppo_carla_lane_create(ppo_carla_rollout_t* r, ppo_carla_lane_t** out);
+int ppo_carla_lane_destroy(ppo_carla_lane_t* l);
+/* :365-381 for one env. HOST pointers (pageable is fine): bev [C, IH, IW], meas [NM], vmeas [NV] (may
+ * be NULL when NV = 0). Stores the observation row and next_done at [step, env], samples with
+ * (env_base = env, step_id = iteration * T + step) — the keys of ppo_carla_rollout_act(step, env,
+ * env + 1), whose stored results it reproduces bit for bit —, stores action / log-prob / value and
+ * returns once action_host[0..A) holds the action. The bev row travels through the lane's pinned buffer
+ * by one DMA straight into its storage row, the fp32 values as kernel arguments (k_carla_lane_in; by
+ * copies when NM + NV exceeds its 62 floats), the action back by one copy followed by a wait on the
+ * lane's stream only. Refused before any HIP call: NULL arguments, a (step, env) outside the storage. */
+int ppo_carla_lane_act(ppo_carla_lane_t* l, int step, int env, const uint8_t* bev, const float* meas,
+                       const float* vmeas, float next_done, float* action_host);
+/* :385: rewards[step, env] = reward, asynchronous on the lane's stream */
+int ppo_carla_lane_reward(ppo_carla_lane_t* l, int step, int env, float reward);
+/* waits for everything the lane has queued */
+int ppo_carla_lane_sync(ppo_carla_lane_t* l);
+
+/* ---- test hook: a lane's k_carla_lane_in launch on caller rows ------------------------------------
+ * meas_row[0..nm) = meas[0..nm), vmeas_row[0..nv) = vmeas[0..nv), *done_row = next_done,
+ * *reward_row = reward: meas / vmeas are HOST arrays, the four rows device pointers; a NULL row is
+ * skipped (vmeas_row with nv = 0, done_row, reward_row). nm + nv <= 62 travels as kernel arguments of
+ * one launch; beyond that every value goes by a copy, as in a lane. Synchronises the stream. */
+int ppo_carla_debug_lane_in(int nm, int nv, const float* meas, const float* vmeas, float next_done, float reward,
+                            float* meas_row, float* vmeas_row, float* done_row, float* reward_row, void* stream);
 
 /* ---- test hooks: the rollout object's gather launches on caller arrays (device pointers) ---------
  * k_carla_gather: dst[i, 0..row_bytes) = src[idx[i], 0..row_bytes) for i < n; rows are packed

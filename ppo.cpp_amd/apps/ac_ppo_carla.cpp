@@ -2,10 +2,12 @@
 // CNN agent trained with PPO against CARLA leaderboard gyms, one env per port (gymcpp/carla_gym.h).
 //
 // Per iteration: linear LR anneal (:348-353); collection of num_steps steps over all envs of the
-// process — one batched ppo_carla_rollout_act per step, then one env step per env (:355-417; the
-// reference runs one thread and one batch-1 forward per env, the agent here serves the process's envs
-// in one forward) —; GAE and update_epochs x num_minibatches optimizer steps on the device
-// (ppo_carla_rollout_gae / _train, include/ppo_carla.h); the reference's log lines ("global_step=...,
+// process (:355-417), in one of two forms (--collect_mode): "lockstep" (default) — one batched
+// ppo_carla_rollout_act per step, then one env step per env, one after the other — or "threads" — the
+// reference's structure: one std::thread and one act lane (ppo_carla_lane_t: a stream and a private set
+// of the forward's buffers) per env, each running its env's steps with batch-1 forwards, so the
+// simulators tick at the same time; joined before the statistics all-reduce —; GAE and update_epochs x
+// num_minibatches optimizer steps on the device (ppo_carla_rollout_gae / _train, include/ppo_carla.h); the reference's log lines ("global_step=...,
 // avg_episodic_return=...", "SPS: ..."), TensorBoard scalars, model_latest_%09d.pth /
 // optimizer_latest_%09d.pth with the previous pair removed (:664-683), model_best.pth /
 // optimizer_best.pth on a new windowed best (:456-474), config.json beside them. --load_file
@@ -240,8 +242,15 @@ int main(int argc, const char** argv) {
   flags.add("logdir", "Folder of the experiment folders", &config.logdir);
   flags.add("exp_name", "Name of the experiment.", &config.exp_name);
   flags.add("rdzv_file", "file used to exchange the RCCL id between ranks", &config.rdzv_file);
+  std::string collect_mode = "lockstep";
+  flags.add("collect_mode",
+            "How the envs of a process are stepped. Options: lockstep (one batched forward per step, envs one after "
+            "the other), threads (one thread and one batch-1 forward per env)",
+            &collect_mode);
   try {
     flags.parse(argc, argv);
+    if (collect_mode != "lockstep" && collect_mode != "threads")
+      throw ParseError("Option 'collect_mode' must be lockstep or threads. Chosen option: " + collect_mode);
     if (config.team_code_folder.empty()) throw ParseError("Option 'team_code_folder' is required");
   } catch (const HelpRequested&) {
     flags.print_help(std::cout);
@@ -424,6 +433,14 @@ int main(int argc, const char** argv) {
     ppo_carla_rollout_t* roll = nullptr;
     check(ppo_carla_rollout_create(agent, &rc, &roll), "ppo_carla_rollout_create");
     check(ppo_carla_rollout_set_iteration(roll, start_step), "ppo_carla_rollout_set_iteration");
+    std::vector<ppo_carla_lane_t*> lanes;  // --collect_mode threads: one per env
+    if (collect_mode == "threads") {
+      if (E > PPO_CARLA_MAX_LANES)
+        throw std::runtime_error("--collect_mode threads serves at most " + std::to_string(PPO_CARLA_MAX_LANES) +
+                                 " envs per process");
+      lanes.resize(E, nullptr);
+      for (int i = 0; i < E; ++i) check(ppo_carla_lane_create(roll, &lanes[i]), "ppo_carla_lane_create");
+    }
     const ppo_carla_train_config tc{config.clip_coef, config.ent_coef, config.vf_coef, config.max_grad_norm,
                                     config.adam_eps, config.norm_adv ? 1 : 0, config.clip_vloss ? 1 : 0};
 
@@ -477,11 +494,63 @@ int main(int argc, const char** argv) {
         lrnow = frac * config.learning_rate;
       }
 
-      // ---- collection (:355-417), the envs of this process in lockstep ----
       float sum_r = 0.0f, sum_l = 0.0f, sum_n = 0.0f;
       std::fill(active.begin(), active.end(), 1);
       std::fill(collected.begin(), collected.end(), T);
-      for (int step = 0; step < T; ++step) {
+      // ---- collection (:355-417), one thread and one lane per env ----
+      if (collect_mode == "threads") {
+        std::vector<float> t_r(E, 0.0f), t_l(E, 0.0f), t_n(E, 0.0f);
+        std::vector<std::string> failed(E);
+        std::vector<std::thread> threads;
+        for (int i = 0; i < E; ++i)
+          threads.emplace_back([&, i] {
+            try {
+              std::vector<float> action((size_t)A);
+              for (int step = 0; step < T; ++step) {
+                check(ppo_carla_lane_act(lanes[i], step, i, h_bev + nb * i, h_f + o_meas + (size_t)NM * i,
+                                         h_f + o_vmeas + (size_t)NV * i, h_f[o_done + i], action.data()),
+                      "ppo_carla_lane_act");
+                auto [state, reward, termination, truncation, infos] = envs[i]->step(action.data());  // :381
+                put_obs(i, state);
+                check(ppo_carla_lane_reward(lanes[i], step, i, reward[0]), "ppo_carla_lane_reward");  // :385
+                h_f[o_done + i] = (termination[0] != 0.0f || truncation[0] != 0.0f) ? 1.0f : 0.0f;   // :383
+                if ((*infos)[0].has_value()) {
+                  t_r[i] += (*infos)[0]->r;
+                  t_l[i] += (float)(*infos)[0]->l;
+                  t_n[i] += 1.0f;
+                }
+                if (config.use_dd_ppo_preempt) {  // :399-407, this env's own store client
+                  const int num_done = tcp_clients[i]->get();
+                  const long min_steps = std::lround(config.dd_ppo_min_perc * static_cast<float>(T));
+                  if (static_cast<float>(num_done) / static_cast<float>(config.num_envs) > config.dd_ppo_preempt_threshold &&
+                      step > min_steps) {
+                    std::cout << "Rank: " + std::to_string(rank) + ", Thread: " + std::to_string(i) +
+                                     ", Preempt at step: " + std::to_string(step) +
+                                     " Num done: " + std::to_string(num_done) + '\n';
+                    active[i] = 0;
+                    collected[i] = step;  // this step is stored, not trained on
+                    tcp_clients[i]->increment();
+                    break;
+                  }
+                }
+              }
+              if (config.use_dd_ppo_preempt && active[i]) tcp_clients[i]->increment();  // :410-412
+            } catch (const std::exception& e) {
+              failed[i] = e.what();
+              if (failed[i].empty()) failed[i] = "collection thread failed";
+            }
+          });
+        for (auto& t : threads) t.join();  // before the statistics all-reduce (:417)
+        for (int i = 0; i < E; ++i)
+          if (!failed[i].empty()) throw std::runtime_error("env " + std::to_string(i) + ": " + failed[i]);
+        for (int i = 0; i < E; ++i) {  // in env order: thread timing does not reach the sums
+          sum_r += t_r[i];
+          sum_l += t_l[i];
+          sum_n += t_n[i];
+        }
+      }
+      // ---- collection (:355-417), the envs of this process in lockstep ----
+      for (int step = 0; collect_mode == "lockstep" && step < T; ++step) {
         int live = 0;
         for (int e0 = 0; e0 < E;) {  // maximal runs of envs that still collect
           if (!active[e0]) { ++e0; continue; }
@@ -525,7 +594,7 @@ int main(int argc, const char** argv) {
         HIPCHECK(hipMemcpy(d_f + o_rew, h_f + o_rew, sizeof(float) * E, hipMemcpyHostToDevice));
         check(ppo_carla_rollout_reward(roll, step, 0, E, d_f + o_rew, nullptr), "ppo_carla_rollout_reward");
       }
-      if (config.use_dd_ppo_preempt)  // :410-412
+      if (config.use_dd_ppo_preempt && collect_mode == "lockstep")  // :410-412
         for (int i = 0; i < E; ++i)
           if (active[i]) tcp_clients[i]->increment();
       const int num_train_steps_per_env = *std::min_element(collected.begin(), collected.end());  // :422-436
@@ -592,6 +661,7 @@ int main(int argc, const char** argv) {
       std::cout << std::flush;
     }
 
+    for (ppo_carla_lane_t* l : lanes) check(ppo_carla_lane_destroy(l), "ppo_carla_lane_destroy");
     ppo_carla_rollout_destroy(roll);
     ppo_carla_destroy(agent);
     (void)hipHostFree(h_bev);

@@ -1604,17 +1604,17 @@ int launch_ln_bwd(int n, int F, float* d, long ds, const float* z, long zs, cons
 // ------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------
-struct ppo_carla {
+// The forward's buffers (activations, split-K partials, conv1's weight table, the tail's barrier, the
+// LayerNorm z / stat) are the base CarlaFwdBufs (ppo_carla_internal.hpp): the agent's own set, which
+// ppo_carla_forward and ppo_carla_update use; an act lane brings its own to carla_forward.
+struct ppo_carla : CarlaFwdBufs {
   ppo_carla_config cfg;
   ppo_carla_layout2 L;  // arch all zero: the offsets of ppo_carla_layout
   int device = 0;
   hipStream_t stream = nullptr;
   float* P = nullptr;
-  float* act[PPO_CARLA_NCONV - 1] = {};  // conv1..conv5 outputs
-  float *enc = nullptr, *s1 = nullptr, *l1 = nullptr, *feat = nullptr, *v1 = nullptr, *v2 = nullptr, *val = nullptr;
-  float *p1 = nullptr, *p2 = nullptr;
-  float* hpre = nullptr;  // [B][2A]
-  float* ksplit = nullptr;  // split-K partials of the forward's narrow layers (conv_split_z)
+  // recorded after every parameter change (carla_params_mark); act lanes wait for it
+  hipEvent_t params_ev = nullptr;
   // training state (allocated on the first ppo_carla_update)
   bool train_ready = false;
   float *G = nullptr, *m = nullptr, *v = nullptr;        // [P]
@@ -1646,27 +1646,14 @@ struct ppo_carla {
   // input stays below this many bytes (0: kWgradFar, the limit of its 32-bit buffer offsets)
   long wgrad_group = 0;
   float *dcol = nullptr, *wt = nullptr, *zbias = nullptr;  // carla_train_init
-  float* c1w = nullptr;  // k_conv_img3's A-operand table
   // MLP tail for n <= kTailMaxN: 1 (default) one launch per stage, 0 one cooperative launch (a grid
   // barrier between stages: slower here, a cooperative launch costs more than the launches it
   // saves), 2 one k_conv / k_conv_fin pair per layer
   int tail_mode = 1;
-  unsigned* tail_bar = nullptr;  // k_carla_tail's grid barrier counter
-  unsigned tail_count = 0;       // arrivals so far (the counter's value between launches)
   // data parallelism (ppo_carla_comm_init): one RCCL communicator, any world >= 1
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
-  // LayerNorm agents (ppo_carla_create2): per normalised layer the pre-activation z [B][F] and the
-  // row statistics {mean, rstd} [B][2]; ln[k].F == 0: the layer has no LayerNorm. lnpart: the column
-  // pass's chunk sums (carla_train_init).
-  struct Ln {
-    int F = 0;
-    long g = -1, be = -1;
-    float *z = nullptr, *stat = nullptr;
-  };
-  enum { kLnConv = 0, kLnS1 = 6, kLnS2, kLnL1, kLnFeat, kLnV1, kLnV2, kLnP1, kLnP2, kLnCount };
-  Ln ln[kLnCount];
-  bool any_ln = false;
+  // LayerNorm agents: the column pass's chunk sums (carla_train_init)
   float* lnpart = nullptr;
   size_t lnpart_floats = 0;
 };
@@ -1676,26 +1663,89 @@ static int carla_alloc(float** p, size_t n) {
   return hipMemset(*p, 0, (n ? n : 1) * sizeof(float)) == hipSuccess ? 0 : -2;
 }
 
+int carla_fwd_alloc(const ppo_carla_t* c, size_t B, CarlaFwdBufs* fb) {
+  const ppo_carla_layout2& L = c->L;
+  int rc = 0;
+  for (int i = 0; i < PPO_CARLA_NCONV - 1; ++i)
+    rc |= carla_alloc(&fb->act[i], B * L.conv_oc[i] * L.conv_oh[i] * L.conv_ow[i]);
+  rc |= carla_alloc(&fb->enc, B * 1280);
+  rc |= carla_alloc(&fb->s1, B * 256);
+  rc |= carla_alloc(&fb->l1, B * 512);
+  rc |= carla_alloc(&fb->feat, B * (256 + L.NV));
+  rc |= carla_alloc(&fb->v1, B * 256);
+  rc |= carla_alloc(&fb->v2, B * 256);
+  rc |= carla_alloc(&fb->val, B);
+  rc |= carla_alloc(&fb->p1, B * 256);
+  rc |= carla_alloc(&fb->p2, B * 256);
+  rc |= carla_alloc(&fb->hpre, B * 2 * L.A);
+  {  // the largest split-K partial buffer of the forward's layers
+    size_t m = 0;
+    auto need = [&](int Kt, int P, int OC) {
+      const int Z = conv_split_z(Kt, P);
+      if (Z > 1) m = std::max(m, (size_t)Z * B * P * OC);
+    };
+    for (int i = 1; i < PPO_CARLA_NCONV; ++i)
+      need(L.conv_ic[i] * L.conv_k[i] * L.conv_k[i], L.conv_oh[i] * L.conv_ow[i], L.conv_oc[i]);
+    need(L.NM, 1, 256); need(256, 1, 256); need(1280, 1, 512); need(512, 1, 256);
+    need(256 + L.NV, 1, 256); need(256, 1, 256); need(256, 1, 1);
+    if (m) rc |= carla_alloc(&fb->ksplit, m);
+  }
+  rc |= carla_alloc(&fb->c1w, (size_t)img3_blocks(L.C, L.conv_k[0]) * 256);
+  rc |= carla_alloc(reinterpret_cast<float**>(&fb->tail_bar), 1);
+  fb->tail_count = 0;
+  {  // pre-activation and statistics buffers of the normalised layers
+    auto ln = [&](int k, int F, long g, long be) {
+      if (g < 0) return;
+      fb->ln[k].F = F;
+      fb->ln[k].g = g;
+      fb->ln[k].be = be;
+      rc |= carla_alloc(&fb->ln[k].z, B * F);
+      rc |= carla_alloc(&fb->ln[k].stat, B * 2);
+      fb->any_ln = true;
+    };
+    for (int i = 0; i < PPO_CARLA_NCONV; ++i)
+      ln(CarlaFwdBufs::kLnConv + i, L.conv_oc[i] * L.conv_oh[i] * L.conv_ow[i], L.conv_g[i], L.conv_be[i]);
+    ln(CarlaFwdBufs::kLnS1, 256, L.st_g[0], L.st_be[0]);
+    ln(CarlaFwdBufs::kLnS2, 256, L.st_g[1], L.st_be[1]);
+    ln(CarlaFwdBufs::kLnL1, 512, L.lin_g[0], L.lin_be[0]);
+    ln(CarlaFwdBufs::kLnFeat, 256, L.lin_g[1], L.lin_be[1]);
+    ln(CarlaFwdBufs::kLnV1, 256, L.v_g[0], L.v_be[0]);
+    ln(CarlaFwdBufs::kLnV2, 256, L.v_g[1], L.v_be[1]);
+    ln(CarlaFwdBufs::kLnP1, 256, L.pi_g[0], L.pi_be[0]);
+    ln(CarlaFwdBufs::kLnP2, 256, L.pi_g[1], L.pi_be[1]);
+  }
+  return rc ? -2 : 0;
+}
+
+void carla_fwd_free(CarlaFwdBufs* fb) {
+  float* bufs[] = {fb->enc, fb->s1, fb->l1,   fb->feat,   fb->v1,  fb->v2,
+                   fb->val, fb->p1, fb->p2,   fb->hpre,   fb->ksplit, fb->c1w, reinterpret_cast<float*>(fb->tail_bar)};
+  for (float* b : bufs)
+    if (b) (void)hipFree(b);
+  for (float* b : fb->act)
+    if (b) (void)hipFree(b);
+  for (auto& l : fb->ln) {
+    if (l.z) (void)hipFree(l.z);
+    if (l.stat) (void)hipFree(l.stat);
+  }
+  *fb = CarlaFwdBufs{};
+}
+
 extern "C" int ppo_carla_destroy(ppo_carla_t* c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) (void)ncclCommDestroy(c->comm);
-  float* bufs[] = {c->P,    c->enc,  c->s1,  c->l1,  c->feat,  c->v1,  c->v2,      c->val,  c->p1,
-                   c->p2,   c->hpre, c->G,   c->m,   c->v,     c->denc, c->ds1,     c->dl1,  c->dfeat,
-                   c->dv1,  c->dv2,  c->dp1, c->dp2, c->dhead, c->dval, c->lp,      c->ent,  c->rowstat,
-                   c->part, c->small,  c->ksplit, c->c1w, c->dcol, c->wt, c->zbias, reinterpret_cast<float*>(c->tail_bar)};
+  float* bufs[] = {c->P,    c->G,    c->m,    c->v,     c->denc, c->ds1,  c->dl1,     c->dfeat, c->dv1,
+                   c->dv2,  c->dp1,  c->dp2,  c->dhead, c->dval, c->lp,   c->ent,     c->rowstat,
+                   c->part, c->small, c->dcol, c->wt,   c->zbias};
   for (float* b : bufs)
     if (b) (void)hipFree(b);
-  for (float* b : c->act)
-    if (b) (void)hipFree(b);
+  carla_fwd_free(c);
   for (float* b : c->dact)
     if (b) (void)hipFree(b);
-  for (auto& l : c->ln) {
-    if (l.z) (void)hipFree(l.z);
-    if (l.stat) (void)hipFree(l.stat);
-  }
   if (c->lnpart) (void)hipFree(c->lnpart);
+  if (c->params_ev) (void)hipEventDestroy(c->params_ev);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;
@@ -1791,55 +1841,9 @@ extern "C" int ppo_carla_create2(const ppo_carla_config* cfg, const ppo_carla_ar
   if (const char* e = getenv("PPO_CARLA_CONV1")) c->conv_img = e[0] - '0';
 #endif
   int rc = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess ? 0 : -2;
-  const size_t B = (size_t)cfg->max_batch;
+  rc |= hipEventCreateWithFlags(&c->params_ev, hipEventDisableTiming) == hipSuccess ? 0 : -2;
   rc |= carla_alloc(&c->P, L.P);
-  for (int i = 0; i < PPO_CARLA_NCONV - 1; ++i)
-    rc |= carla_alloc(&c->act[i], B * L.conv_oc[i] * L.conv_oh[i] * L.conv_ow[i]);
-  rc |= carla_alloc(&c->enc, B * 1280);
-  rc |= carla_alloc(&c->s1, B * 256);
-  rc |= carla_alloc(&c->l1, B * 512);
-  rc |= carla_alloc(&c->feat, B * (256 + L.NV));
-  rc |= carla_alloc(&c->v1, B * 256);
-  rc |= carla_alloc(&c->v2, B * 256);
-  rc |= carla_alloc(&c->val, B);
-  rc |= carla_alloc(&c->p1, B * 256);
-  rc |= carla_alloc(&c->p2, B * 256);
-  rc |= carla_alloc(&c->hpre, B * 2 * L.A);
-  {  // the largest split-K partial buffer of the forward's layers
-    size_t m = 0;
-    auto need = [&](int Kt, int P, int OC) {
-      const int Z = conv_split_z(Kt, P);
-      if (Z > 1) m = std::max(m, (size_t)Z * B * P * OC);
-    };
-    for (int i = 1; i < PPO_CARLA_NCONV; ++i)
-      need(L.conv_ic[i] * L.conv_k[i] * L.conv_k[i], L.conv_oh[i] * L.conv_ow[i], L.conv_oc[i]);
-    need(L.NM, 1, 256); need(256, 1, 256); need(1280, 1, 512); need(512, 1, 256);
-    need(256 + L.NV, 1, 256); need(256, 1, 256); need(256, 1, 1);
-    if (m) rc |= carla_alloc(&c->ksplit, m);
-  }
-  rc |= carla_alloc(&c->c1w, (size_t)img3_blocks(L.C, L.conv_k[0]) * 256);
-  rc |= carla_alloc(reinterpret_cast<float**>(&c->tail_bar), 1);
-  {  // pre-activation and statistics buffers of the normalised layers
-    auto ln = [&](int k, int F, long g, long be) {
-      if (g < 0) return;
-      c->ln[k].F = F;
-      c->ln[k].g = g;
-      c->ln[k].be = be;
-      rc |= carla_alloc(&c->ln[k].z, B * F);
-      rc |= carla_alloc(&c->ln[k].stat, B * 2);
-      c->any_ln = true;
-    };
-    for (int i = 0; i < PPO_CARLA_NCONV; ++i)
-      ln(ppo_carla::kLnConv + i, L.conv_oc[i] * L.conv_oh[i] * L.conv_ow[i], L.conv_g[i], L.conv_be[i]);
-    ln(ppo_carla::kLnS1, 256, L.st_g[0], L.st_be[0]);
-    ln(ppo_carla::kLnS2, 256, L.st_g[1], L.st_be[1]);
-    ln(ppo_carla::kLnL1, 512, L.lin_g[0], L.lin_be[0]);
-    ln(ppo_carla::kLnFeat, 256, L.lin_g[1], L.lin_be[1]);
-    ln(ppo_carla::kLnV1, 256, L.v_g[0], L.v_be[0]);
-    ln(ppo_carla::kLnV2, 256, L.v_g[1], L.v_be[1]);
-    ln(ppo_carla::kLnP1, 256, L.pi_g[0], L.pi_be[0]);
-    ln(ppo_carla::kLnP2, 256, L.pi_g[1], L.pi_be[1]);
-  }
+  rc |= carla_fwd_alloc(c, (size_t)cfg->max_batch, c);
   if (rc || hipDeviceSynchronize() != hipSuccess) {
     ppo_carla_destroy(c);
     return ppo_fail("ppo_carla_create: device allocation failed", -2);
@@ -1883,7 +1887,7 @@ extern "C" int ppo_carla_load_params(ppo_carla_t* c, const float* host, long n) 
       hipMemcpyAsync(c->P, host, sizeof(float) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return ppo_fail("ppo_carla_load_params: copy failed", -2);
-  return 0;
+  return carla_params_mark(c, c->stream);
 }
 
 extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, const float* meas, const float* vmeas,
@@ -1896,14 +1900,21 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
   if (sample_type < PPO_CARLA_SAMPLE || sample_type > PPO_CARLA_ROACH)
     return ppo_fail("Unsupported sample type used. Sample type: " + std::to_string(sample_type), -1);
   if (sample_type == PPO_CARLA_GIVEN && !action_in) return ppo_fail("ppo_carla_forward: GIVEN needs action_in", -1);
+  if (hipSetDevice(c->device) != hipSuccess) return ppo_fail("ppo_carla_forward: hipSetDevice failed", -2);
+  return carla_forward(c, *c, stream ? (hipStream_t)stream : c->stream, n, bev, meas, vmeas, sample_type, action_in,
+                       env_base, step_id, action, logprob, entropy, value, alpha, beta);
+}
+
+int carla_forward(const ppo_carla_t* c, CarlaFwdBufs& fb, hipStream_t s, int n, const uint8_t* bev, const float* meas,
+                  const float* vmeas, int sample_type, const float* action_in, long env_base, long step_id,
+                  float* action, float* logprob, float* entropy, float* value, float* alpha, float* beta) {
   const ppo_carla_layout2& L = c->L;
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const float* P = c->P;
   auto conv = [&](const float* in_f, const uint8_t* in_u8, long in_stride, int IC, int IH, int IW, long w, long b,
                   float* out, long out_stride, int OC, int OH, int OW, int K, int S, int relu) {
     ConvArgs a{in_f, in_u8, in_stride, IC, IH, IW, P + w, P + b, out, out_stride, OC, OH, OW, K, S, relu, n,
-               c->ksplit, 0};
-    a.wprep = c->c1w;
+               fb.ksplit, 0};
+    a.wprep = fb.c1w;
     a.bx = c->c1bx;
     a.tiled = c->conv_t;
     return launch_conv(a, s, c->conv_img);
@@ -1912,13 +1923,13 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
                     int relu) { return conv(in, nullptr, in_stride, IN, 1, 1, w, b, out, out_stride, OUT, 1, 1, 1, 1, relu); };
   // a normalised layer: the pre-activation goes to ln[k].z, k_carla_ln writes the layer's output
   auto norm = [&](int k, float* out, long out_stride) {
-    const ppo_carla::Ln& l = c->ln[k];
+    const CarlaFwdBufs::Ln& l = fb.ln[k];
     launch_ln_fwd(n, l.F, l.z, l.F, P + l.g, P + l.be, out, out_stride, l.stat, s);
   };
   auto linear_act = [&](int k, const float* in, long in_stride, int IN, long w, long b, float* out, long out_stride,
                         int OUT) {
-    if (!c->ln[k].F) return linear(in, in_stride, IN, w, b, out, out_stride, OUT, 1);
-    const int r = linear(in, in_stride, IN, w, b, c->ln[k].z, OUT, OUT, 0);
+    if (!fb.ln[k].F) return linear(in, in_stride, IN, w, b, out, out_stride, OUT, 1);
+    const int r = linear(in, in_stride, IN, w, b, fb.ln[k].z, OUT, OUT, 0);
     norm(k, out, out_stride);
     return r;
   };
@@ -1933,15 +1944,15 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
   long cur_stride = (long)L.C * L.IH * L.IW;
   for (int i = 0; i < PPO_CARLA_NCONV; ++i) {
     const bool last = i == PPO_CARLA_NCONV - 1;
-    float* out = last ? c->enc : c->act[i];
+    float* out = last ? fb.enc : fb.act[i];
     const long out_stride = last ? 1280 : (long)L.conv_oc[i] * L.conv_oh[i] * L.conv_ow[i];
     if (last && fused_tail) {  // conv6's split-K finish moves into the tail's stage 0
       c6 = ConvArgs{cur, nullptr, cur_stride, L.conv_ic[i], L.conv_ih[i], L.conv_iw[i], P + L.conv_w[i],
                     P + L.conv_b[i], out, out_stride, L.conv_oc[i], L.conv_oh[i], L.conv_ow[i], L.conv_k[i],
-                    L.conv_s[i], 1, n, c->ksplit, 0};
+                    L.conv_s[i], 1, n, fb.ksplit, 0};
       rc |= launch_conv(c6, s, c->conv_img, false, &c6_Z);
-    } else if (c->ln[ppo_carla::kLnConv + i].F) {  // roach_ln: conv -> LayerNorm([OC, OH, OW]) -> ReLU
-      const ppo_carla::Ln& l = c->ln[ppo_carla::kLnConv + i];
+    } else if (fb.ln[ppo_carla::kLnConv + i].F) {  // roach_ln: conv -> LayerNorm([OC, OH, OW]) -> ReLU
+      const CarlaFwdBufs::Ln& l = fb.ln[ppo_carla::kLnConv + i];
       rc |= conv(cur, img, cur_stride, L.conv_ic[i], L.conv_ih[i], L.conv_iw[i], L.conv_w[i], L.conv_b[i], l.z, l.F,
                  L.conv_oc[i], L.conv_oh[i], L.conv_ow[i], L.conv_k[i], L.conv_s[i], 0);
       norm(ppo_carla::kLnConv + i, out, out_stride);
@@ -1961,7 +1972,7 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
     ta.c6 = c6;
     ta.c6_Z = c6_Z;
     ta.vmeas = vmeas;
-    ta.feat = c->feat;
+    ta.feat = fb.feat;
     ta.NV = L.NV;
     auto lin = [&](int stage, const float* in, long in_stride, int K, long w, long b, float* out, long out_stride,
                    int OC, int relu, float* out2) {
@@ -1974,33 +1985,33 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
     const int d = L.NM <= kTailPreMaxK ? 1 : 0;
     ta.pre_lin = ta.pre_for = -1;
     if (d) ta.pre_lin = ta.nlin;
-    lin(d ? -1 : 0, meas, L.NM, L.NM, L.st_w[0], L.st_b[0], c->s1, 256, 256, 1, nullptr);
+    lin(d ? -1 : 0, meas, L.NM, L.NM, L.st_w[0], L.st_b[0], fb.s1, 256, 256, 1, nullptr);
     if (d) ta.pre_for = ta.nlin;
-    lin(1 - d, c->s1, 256, 256, L.st_w[1], L.st_b[1], c->enc + 1024, 1280, 256, 1, nullptr);
-    lin(2 - d, c->enc, 1280, 1280, L.lin_w[0], L.lin_b[0], c->l1, 512, 512, 1, nullptr);
-    lin(3 - d, c->l1, 512, 512, L.lin_w[1], L.lin_b[1], c->feat, FW, 256, 1, nullptr);
-    lin(4 - d, c->feat, FW, (int)FW, L.v_w[0], L.v_b[0], c->v1, 256, 256, 1, nullptr);
-    lin(4 - d, c->feat, FW, 256, L.pi_w[0], L.pi_b[0], c->p1, 256, 256, 1, nullptr);
-    lin(5 - d, c->v1, 256, 256, L.v_w[1], L.v_b[1], c->v2, 256, 256, 1, nullptr);
-    lin(5 - d, c->p1, 256, 256, L.pi_w[1], L.pi_b[1], c->p2, 256, 256, 1, nullptr);
-    lin(6 - d, c->v2, 256, 256, L.v_w[2], L.v_b[2], c->val, 1, 1, 0, value);
+    lin(1 - d, fb.s1, 256, 256, L.st_w[1], L.st_b[1], fb.enc + 1024, 1280, 256, 1, nullptr);
+    lin(2 - d, fb.enc, 1280, 1280, L.lin_w[0], L.lin_b[0], fb.l1, 512, 512, 1, nullptr);
+    lin(3 - d, fb.l1, 512, 512, L.lin_w[1], L.lin_b[1], fb.feat, FW, 256, 1, nullptr);
+    lin(4 - d, fb.feat, FW, (int)FW, L.v_w[0], L.v_b[0], fb.v1, 256, 256, 1, nullptr);
+    lin(4 - d, fb.feat, FW, 256, L.pi_w[0], L.pi_b[0], fb.p1, 256, 256, 1, nullptr);
+    lin(5 - d, fb.v1, 256, 256, L.v_w[1], L.v_b[1], fb.v2, 256, 256, 1, nullptr);
+    lin(5 - d, fb.p1, 256, 256, L.pi_w[1], L.pi_b[1], fb.p2, 256, 256, 1, nullptr);
+    lin(6 - d, fb.v2, 256, 256, L.v_w[2], L.v_b[2], fb.val, 1, 1, 0, value);
     ta.nstage = 7 - d;
     ta.head_stage = 6 - d;
     ta.h = HeadArgs{P,          L.mu_w, L.mu_b,   L.sg_w,    L.sg_b,    L.hi,    L.lo,
-                    c->p2,      c->val, n,        L.A,       sample_type, c->cfg.beta_min, action_in,
+                    fb.p2,      fb.val, n,        L.A,       sample_type, c->cfg.beta_min, action_in,
                     c->cfg.seed, c->cfg.rank, env_base, step_id, action, logprob, entropy, value, alpha, beta,
-                    c->hpre};
-    ta.bar = c->tail_bar;
+                    fb.hpre};
+    ta.bar = fb.tail_bar;
     const int rt_n = (n + 15) / 16;
     const unsigned G = (unsigned)(rt_n * 32);  // linear.0's work items (512 / 16 output tiles)
     if (c->tail_mode == 0) {
       ta.stage_lo = 0;
       ta.stage_hi = ta.nstage - 1;
-      ta.bar_base = c->tail_count;
+      ta.bar_base = fb.tail_count;
       void* args[] = {&ta};
       if (hipLaunchCooperativeKernel((const void*)k_carla_tail, dim3(G), dim3(kTailThreads), args, 0, s) != hipSuccess)
         return ppo_fail("ppo_carla_forward: cooperative launch of the fused tail failed", -2);
-      c->tail_count += (unsigned)(ta.nstage - 1) * G;
+      fb.tail_count += (unsigned)(ta.nstage - 1) * G;
     } else {
       for (int st = 0; st < ta.nstage; ++st) {
         ta.stage_lo = ta.stage_hi = st;
@@ -2011,23 +2022,23 @@ extern "C" int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, cons
     return 0;
   }
   // state_linear (:238) -> columns 1024..1279; linear (:240) -> features = value-head input columns 0..255
-  rc |= linear_act(ppo_carla::kLnS1, meas, L.NM, L.NM, L.st_w[0], L.st_b[0], c->s1, 256, 256);
-  rc |= linear_act(ppo_carla::kLnS2, c->s1, 256, 256, L.st_w[1], L.st_b[1], c->enc + 1024, 1280, 256);
-  rc |= linear_act(ppo_carla::kLnL1, c->enc, 1280, 1280, L.lin_w[0], L.lin_b[0], c->l1, 512, 512);
-  rc |= linear_act(ppo_carla::kLnFeat, c->l1, 512, 512, L.lin_w[1], L.lin_b[1], c->feat, FW, 256);
+  rc |= linear_act(ppo_carla::kLnS1, meas, L.NM, L.NM, L.st_w[0], L.st_b[0], fb.s1, 256, 256);
+  rc |= linear_act(ppo_carla::kLnS2, fb.s1, 256, 256, L.st_w[1], L.st_b[1], fb.enc + 1024, 1280, 256);
+  rc |= linear_act(ppo_carla::kLnL1, fb.enc, 1280, 1280, L.lin_w[0], L.lin_b[0], fb.l1, 512, 512);
+  rc |= linear_act(ppo_carla::kLnFeat, fb.l1, 512, 512, L.lin_w[1], L.lin_b[1], fb.feat, FW, 256);
   if (L.NV > 0)
-    hipLaunchKernelGGL(k_carla_pack, dim3((n * L.NV + 255) / 256), dim3(256), 0, s, vmeas, c->feat, n, L.NV);
+    hipLaunchKernelGGL(k_carla_pack, dim3((n * L.NV + 255) / 256), dim3(256), 0, s, vmeas, fb.feat, n, L.NV);
   // value_head on [features | value_measurements] (:276-277), policy_head on features (:279)
-  rc |= linear_act(ppo_carla::kLnV1, c->feat, FW, (int)FW, L.v_w[0], L.v_b[0], c->v1, 256, 256);
-  rc |= linear_act(ppo_carla::kLnV2, c->v1, 256, 256, L.v_w[1], L.v_b[1], c->v2, 256, 256);
-  rc |= linear(c->v2, 256, 256, L.v_w[2], L.v_b[2], c->val, 1, 1, 0);
-  rc |= linear_act(ppo_carla::kLnP1, c->feat, FW, 256, L.pi_w[0], L.pi_b[0], c->p1, 256, 256);
-  rc |= linear_act(ppo_carla::kLnP2, c->p1, 256, 256, L.pi_w[1], L.pi_b[1], c->p2, 256, 256);
+  rc |= linear_act(ppo_carla::kLnV1, fb.feat, FW, (int)FW, L.v_w[0], L.v_b[0], fb.v1, 256, 256);
+  rc |= linear_act(ppo_carla::kLnV2, fb.v1, 256, 256, L.v_w[1], L.v_b[1], fb.v2, 256, 256);
+  rc |= linear(fb.v2, 256, 256, L.v_w[2], L.v_b[2], fb.val, 1, 1, 0);
+  rc |= linear_act(ppo_carla::kLnP1, fb.feat, FW, 256, L.pi_w[0], L.pi_b[0], fb.p1, 256, 256);
+  rc |= linear_act(ppo_carla::kLnP2, fb.p1, 256, 256, L.pi_w[1], L.pi_b[1], fb.p2, 256, 256);
   if (rc) return ppo_fail("ppo_carla_forward: no convolution kernel for this shape", -1);
   HeadArgs h{P,          L.mu_w, L.mu_b,   L.sg_w,    L.sg_b,    L.hi,    L.lo,
-             c->p2,      c->val, n,        L.A,       sample_type, c->cfg.beta_min, action_in,
+             fb.p2,      fb.val, n,        L.A,       sample_type, c->cfg.beta_min, action_in,
              c->cfg.seed, c->cfg.rank, env_base, step_id, action, logprob, entropy, value, alpha, beta,
-             c->hpre};
+             fb.hpre};
   hipLaunchKernelGGL(k_carla_head, dim3((n + 63) / 64), dim3(64), 0, s, h);
   if (hipGetLastError() != hipSuccess) return ppo_fail("ppo_carla_forward: launch failed", -2);
   return 0;
@@ -3928,6 +3939,7 @@ extern "C" int ppo_carla_update(ppo_carla_t* c, const ppo_carla_train_config* tc
   hipLaunchKernelGGL(k_carla_adam, dim3((unsigned)((L.P - begin + 255) / 256)), dim3(256), 0, s, ad);
   hipLaunchKernelGGL(k_carla_stats, dim3(1), dim3(256), 0, s, c->rowstat, n, sm + 64);
   if (hipGetLastError() != hipSuccess) return ppo_fail("ppo_carla_update: launch failed", -2);
+  if (int mrc = carla_params_mark(c, s)) return mrc;  // act lanes read the parameters after this step
   if (stats) {
     // loss statistics averaged over ranks (ac_ppo_carla.cpp:645-651); the total norm is global already
     if (c->comm && ncclAllReduce(sm + 64, sm + 64, 6, ncclFloat, ncclAvg, c->comm, s) != ncclSuccess)
@@ -4022,6 +4034,7 @@ extern "C" int ppo_carla_comm_broadcast_params(ppo_carla_t* c, int root) {
   if (hipSetDevice(c->device) != hipSuccess) return ppo_fail("ppo_carla_comm_broadcast_params: hipSetDevice failed", -2);
   if (ncclBroadcast(c->P, c->P, (size_t)c->L.P, ncclFloat, root, c->comm, c->stream) != ncclSuccess)
     return ppo_fail("ppo_carla_comm_broadcast_params: ncclBroadcast failed", -3);
+  if (int rc = carla_params_mark(c, c->stream)) return rc;
   return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : ppo_fail("ppo_carla_comm_broadcast_params: sync failed", -2);
 }
 
@@ -4077,6 +4090,17 @@ extern "C" int ppo_carla_debug_ln_backward(int n, int F, const float* z, long in
 int carla_agent_info(const ppo_carla_t* c, CarlaAgentInfo* out) {
   if (!c || !out) return ppo_fail("carla_agent_info: null argument", -1);
   *out = CarlaAgentInfo{c->device, c->cfg.max_batch, c->stream};
+  return 0;
+}
+
+int carla_params_mark(ppo_carla_t* c, hipStream_t s) {
+  if (hipEventRecord(c->params_ev, s) != hipSuccess) return ppo_fail("carla_params_mark: hipEventRecord failed", -2);
+  return 0;
+}
+
+int carla_params_wait(const ppo_carla_t* c, hipStream_t s) {
+  if (hipStreamWaitEvent(s, c->params_ev, 0) != hipSuccess)
+    return ppo_fail("carla_params_wait: hipStreamWaitEvent failed", -2);
   return 0;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstring>
 #include <string>
@@ -160,7 +161,119 @@ struct ppo_carla_rollout {
         *mb_ret = nullptr, *mb_values = nullptr;
   int32_t* perms = nullptr;  // [update_epochs][B]
   float* slots = nullptr;    // [update_epochs * num_minibatches][kCarlaStatSlot], then fin [8]
+  // act lanes (ppo_carla.h "act lanes"). lanes: created and destroyed under the exclusive flag only.
+  // sync_ev: recorded after every gae / train; a lane's next act waits for it before it writes storage rows.
+  ppo_carla_lane_t* lanes[PPO_CARLA_MAX_LANES] = {};
+  hipEvent_t sync_ev = nullptr;
+  std::atomic<int> lane_calls{0};  // lane calls inside the library
+  std::atomic<int> exclusive{0};   // 1 while gae / train / lane_create / lane_destroy is inside the library
 };
+
+struct ppo_carla_lane {
+  ppo_carla_rollout_t* r = nullptr;
+  int slot = -1;  // index in r->lanes
+  hipStream_t stream = nullptr;
+  hipEvent_t ev = nullptr;  // after the last work queued on stream
+  CarlaFwdBufs fb;          // one row
+  uint8_t* pin = nullptr;   // pinned: bev row | action [A] | meas [NM] | vmeas [NV] | done | reward
+  float* pin_f = nullptr;   // the floats of pin
+};
+
+namespace {
+
+// Both guards are sequentially consistent counters: a lane call announces itself, then looks for an
+// exclusive call; an exclusive call announces itself, then looks for lane calls. Whichever comes second
+// sees the other, so of two calls that overlap at least one is refused.
+struct LaneCallGuard {
+  ppo_carla_rollout_t* r;
+  bool ok;
+  explicit LaneCallGuard(ppo_carla_rollout_t* r_) : r(r_) {
+    r->lane_calls.fetch_add(1);
+    ok = r->exclusive.load() == 0;
+  }
+  ~LaneCallGuard() { r->lane_calls.fetch_sub(1); }
+};
+struct ExclusiveGuard {
+  ppo_carla_rollout_t* r;
+  bool ok;
+  explicit ExclusiveGuard(ppo_carla_rollout_t* r_) : r(r_) {
+    ok = r->exclusive.exchange(1) == 0;
+    if (ok && r->lane_calls.load() != 0) {
+      r->exclusive.store(0);
+      ok = false;
+    }
+  }
+  ~ExclusiveGuard() {
+    if (ok) r->exclusive.store(0);
+  }
+};
+
+// the stream of a gae / train call waits for what every lane has queued
+int r_wait_lanes(ppo_carla_rollout_t* r, hipStream_t s) {
+  for (ppo_carla_lane_t* l : r->lanes)
+    if (l && hipStreamWaitEvent(s, l->ev, 0) != hipSuccess) return -2;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_carla_lane_in: the small fp32 inputs of one act (or one reward) into their storage rows
+// ------------------------------------------------------------------------------------------
+// meas [NM], vmeas [NV], next_done and reward of one env are at most a few dozen floats: they travel in
+// the kernel's argument block, and one wave writes them with one vector store per lane. That replaces
+// three host-to-device copies of 32, 12 and 4 bytes per act (each a DMA submission) by one launch on
+// the lane's stream. A NULL destination is skipped.
+constexpr int kLaneInMax = 62;  // floats of meas + vmeas in the argument block (a 64-lane wave writes them)
+struct LaneInArgs {
+  float *meas, *vmeas, *done, *reward;  // destination rows
+  int nm, nv;
+  float done_v, reward_v;
+  float v[kLaneInMax];  // meas, then vmeas
+};
+__global__ __launch_bounds__(64) void k_carla_lane_in(LaneInArgs a) {
+  const int t = threadIdx.x;
+  if (t < a.nm) a.meas[t] = a.v[t];
+  else if (t < a.nm + a.nv && a.vmeas) a.vmeas[t - a.nm] = a.v[t];
+  if (t == 62 && a.done) *a.done = a.done_v;
+  if (t == 63 && a.reward) *a.reward = a.reward_v;
+}
+
+// host values -> rows on s. stage: host memory the copies of the wide path may read after the call
+// returns (a lane's pinned buffer), nm + nv + 2 floats, or nullptr: the sources are read before return.
+int lane_in(int nm, int nv, const float* meas, const float* vmeas, float done_v, float reward_v, float* meas_row,
+            float* vmeas_row, float* done_row, float* reward_row, float* stage, hipStream_t s) {
+  if (!vmeas_row) nv = 0;
+  if (!meas_row) nm = 0;
+  if (nm + nv <= kLaneInMax) {
+    LaneInArgs a{};
+    a.meas = meas_row; a.vmeas = vmeas_row; a.done = done_row; a.reward = reward_row;
+    a.nm = nm; a.nv = nv; a.done_v = done_v; a.reward_v = reward_v;
+    for (int i = 0; i < nm; ++i) a.v[i] = meas[i];
+    for (int i = 0; i < nv; ++i) a.v[nm + i] = vmeas[i];
+    hipLaunchKernelGGL(k_carla_lane_in, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  // wider than the argument block: one copy per array
+  const size_t f = sizeof(float);
+  float local[2] = {done_v, reward_v};
+  const float *m = meas, *v = vmeas, *dr = local;
+  if (stage) {
+    if (nm) memcpy(stage, meas, nm * f);
+    if (nv) memcpy(stage + nm, vmeas, nv * f);
+    stage[nm + nv] = done_v;
+    stage[nm + nv + 1] = reward_v;
+    m = stage; v = stage + nm; dr = stage + nm + nv;
+  }
+  bool ok = true;
+  if (nm) ok = ok && hipMemcpyAsync(meas_row, m, nm * f, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (nv) ok = ok && hipMemcpyAsync(vmeas_row, v, nv * f, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (done_row) ok = ok && hipMemcpyAsync(done_row, dr, f, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (reward_row) ok = ok && hipMemcpyAsync(reward_row, dr + 1, f, hipMemcpyHostToDevice, s) == hipSuccess;
+  // without a staging buffer the sources are the caller's (or this frame's): they must have been read
+  if (!stage) ok = ok && hipStreamSynchronize(s) == hipSuccess;
+  return ok ? 0 : -2;
+}
+
+}  // namespace
 
 static int r_alloc(void** p, size_t bytes) {
   if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) return -2;
@@ -176,6 +289,9 @@ extern "C" int ppo_carla_rollout_destroy(ppo_carla_rollout_t* r) {
                   r->mb_actions, r->mb_logp, r->mb_adv, r->mb_ret,  r->mb_values, r->perms, r->slots};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  if (r->sync_ev) (void)hipEventDestroy(r->sync_ev);
+  for (ppo_carla_lane_t* l : r->lanes)  // a lane left behind: its handle dangles from here on
+    if (l) l->r = nullptr;
   delete r;
   return 0;
 }
@@ -229,6 +345,7 @@ extern "C" int ppo_carla_rollout_create(ppo_carla_t* agent, const ppo_carla_roll
   for (float** p : {&r->mb_logp, &r->mb_adv, &r->mb_ret, &r->mb_values}) bad |= r_alloc((void**)p, uM * f);
   bad |= r_alloc((void**)&r->perms, (size_t)cfg->update_epochs * uB * sizeof(int32_t));
   bad |= r_alloc((void**)&r->slots, ((size_t)nslots + 1) * kCarlaStatSlot * f);
+  bad |= hipEventCreateWithFlags(&r->sync_ev, hipEventDisableTiming) == hipSuccess ? 0 : 1;
   // the zero fills above ran on the null stream; the agent's stream does not wait for it
   if (!bad && hipDeviceSynchronize() != hipSuccess) bad = 1;
   if (bad) {
@@ -297,8 +414,11 @@ extern "C" int ppo_carla_rollout_gae(ppo_carla_rollout_t* r, const uint8_t* next
     return ppo_fail("ppo_carla_rollout_gae: null argument", -1);
   if (num_steps_collected <= 0 || num_steps_collected > r->T)
     return ppo_fail("ppo_carla_rollout_gae: bad collected step count", -1);
+  ExclusiveGuard guard(r);
+  if (!guard.ok) return ppo_fail("ppo_carla_rollout_gae: called while a lane call is inside the library", -1);
   if (hipSetDevice(r->info.device) != hipSuccess) return ppo_fail("ppo_carla_rollout_gae: hipSetDevice failed", -2);
   hipStream_t s = r_stream(r, stream);
+  if (r_wait_lanes(r, s)) return ppo_fail("ppo_carla_rollout_gae: waiting for the lanes failed", -2);
   // :486 get_value on the next observation
   int rc = ppo_carla_forward(r->agent, (int)r->E, next_bev, next_meas, next_vmeas, PPO_CARLA_MEAN, nullptr, 0, 0,
                              nullptr, nullptr, nullptr, r->next_value, nullptr, nullptr, s);
@@ -322,6 +442,7 @@ extern "C" int ppo_carla_rollout_gae(ppo_carla_rollout_t* r, const uint8_t* next
   g.lam = r->cfg.gae_lambda;
   launch_gae(g, s);  // writes returns = advantages + values with the advantages (:503)
   if (hipGetLastError() != hipSuccess) return ppo_fail("ppo_carla_rollout_gae: launch failed", -2);
+  if (hipEventRecord(r->sync_ev, s) != hipSuccess) return ppo_fail("ppo_carla_rollout_gae: hipEventRecord failed", -2);
   return 0;
 }
 
@@ -331,8 +452,11 @@ extern "C" int ppo_carla_rollout_train(ppo_carla_rollout_t* r, const ppo_carla_t
   if (!r || !tc) return ppo_fail("ppo_carla_rollout_train: null argument", -1);
   if (num_steps_collected <= 0 || num_steps_collected > r->T)
     return ppo_fail("ppo_carla_rollout_train: bad collected step count", -1);
+  ExclusiveGuard guard(r);
+  if (!guard.ok) return ppo_fail("ppo_carla_rollout_train: called while a lane call is inside the library", -1);
   if (hipSetDevice(r->info.device) != hipSuccess) return ppo_fail("ppo_carla_rollout_train: hipSetDevice failed", -2);
   hipStream_t s = r->info.stream;
+  if (r_wait_lanes(r, s)) return ppo_fail("ppo_carla_rollout_train: waiting for the lanes failed", -2);
   const int EP = r->cfg.update_epochs, MB = r->cfg.num_minibatches;
   const long B = r->B, M = r->M, Bc = (long)num_steps_collected * r->E;
   // ---- permutations (:532-538), as ppo_update_ex ----
@@ -377,6 +501,8 @@ extern "C" int ppo_carla_rollout_train(ppo_carla_rollout_t* r, const ppo_carla_t
       if (rc) return rc;
     }
   r->iteration += 1;
+  // the gathers above read the storage rows a lane's next act overwrites
+  if (hipEventRecord(r->sync_ev, s) != hipSuccess) return ppo_fail("ppo_carla_rollout_train: hipEventRecord failed", -2);
   if (last || mean_clipfrac) {
     const int nslots = EP * MB;
     float* fin = r->slots + (size_t)nslots * kCarlaStatSlot;
@@ -429,8 +555,153 @@ extern "C" int ppo_carla_rollout_set_iteration(ppo_carla_rollout_t* r, long iter
 }
 
 // ------------------------------------------------------------------------------------------
+// act lanes (ppo_carla.h "act lanes"): ac_ppo_carla.cpp:355-417, one thread / stream / forward per env
+// ------------------------------------------------------------------------------------------
+static void lane_free(ppo_carla_lane_t* l) {
+  carla_fwd_free(&l->fb);
+  if (l->pin) (void)hipHostFree(l->pin);
+  if (l->ev) (void)hipEventDestroy(l->ev);
+  if (l->stream) (void)hipStreamDestroy(l->stream);
+  delete l;
+}
+
+extern "C" int ppo_carla_lane_create(ppo_carla_rollout_t* r, ppo_carla_lane_t** out) {
+  if (!r || !out) return ppo_fail("ppo_carla_lane_create: null argument", -1);
+  ExclusiveGuard guard(r);
+  if (!guard.ok) return ppo_fail("ppo_carla_lane_create: called while another call on the object is inside the library", -1);
+  int slot = 0;
+  while (slot < PPO_CARLA_MAX_LANES && r->lanes[slot]) ++slot;
+  if (slot == PPO_CARLA_MAX_LANES)
+    return ppo_fail("ppo_carla_lane_create: a rollout object has at most " + std::to_string(PPO_CARLA_MAX_LANES) +
+                    " lanes", -1);
+  if (hipSetDevice(r->info.device) != hipSuccess) return ppo_fail("ppo_carla_lane_create: hipSetDevice failed", -2);
+  ppo_carla_lane_t* l = new ppo_carla_lane_t();
+  l->r = r;
+  l->slot = slot;
+  // bev row, padded to whole floats, then action | meas | vmeas | done | reward
+  const size_t bev_pad = ((size_t)r->row_bytes + 15) & ~(size_t)15;
+  const size_t nfl = (size_t)r->A + r->NM + r->NV + 2;
+  bool ok = hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&l->ev, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipHostMalloc((void**)&l->pin, bev_pad + nfl * sizeof(float), hipHostMallocDefault) == hipSuccess;
+  ok = ok && carla_fwd_alloc(r->agent, 1, &l->fb) == 0;
+  // the zero fills of the buffers ran on the null stream; the lane's stream does not wait for it
+  ok = ok && hipDeviceSynchronize() == hipSuccess;
+  if (!ok) {
+    lane_free(l);
+    return ppo_fail("ppo_carla_lane_create: allocation failed", -2);
+  }
+  l->pin_f = reinterpret_cast<float*>(l->pin + bev_pad);
+  r->lanes[slot] = l;
+  *out = l;
+  return 0;
+}
+
+extern "C" int ppo_carla_lane_destroy(ppo_carla_lane_t* l) {
+  if (!l) return 0;
+  ppo_carla_rollout_t* r = l->r;
+  if (r) {
+    ExclusiveGuard guard(r);
+    if (!guard.ok)
+      return ppo_fail("ppo_carla_lane_destroy: called while another call on the object is inside the library", -1);
+    (void)hipSetDevice(r->info.device);
+    (void)hipStreamSynchronize(l->stream);
+    r->lanes[l->slot] = nullptr;
+    lane_free(l);
+    return 0;
+  }
+  (void)hipStreamSynchronize(l->stream);  // the rollout object went first
+  lane_free(l);
+  return 0;
+}
+
+// the checks every lane call starts with, none of which needs the device
+static int lane_check(const ppo_carla_lane_t* l, int step, int env, const char* what) {
+  if (!l->r) return ppo_fail(std::string(what) + ": the lane's rollout object was destroyed", -1);
+  if (step < 0 || step >= l->r->T) return ppo_fail(std::string(what) + ": step out of range", -1);
+  if (env < 0 || env >= l->r->E) return ppo_fail(std::string(what) + ": env out of range", -1);
+  return 0;
+}
+
+extern "C" int ppo_carla_lane_act(ppo_carla_lane_t* l, int step, int env, const uint8_t* bev, const float* meas,
+                                  const float* vmeas, float next_done, float* action_host) {
+  if (!l || !bev || !meas || !action_host || (l->r && !vmeas && l->r->NV > 0))
+    return ppo_fail("ppo_carla_lane_act: null argument", -1);
+  if (int rc = lane_check(l, step, env, "ppo_carla_lane_act")) return rc;
+  ppo_carla_rollout_t* r = l->r;
+  LaneCallGuard guard(r);
+  if (!guard.ok) return ppo_fail("ppo_carla_lane_act: called while gae, train or a lane's creation is inside the library", -1);
+  if (hipSetDevice(r->info.device) != hipSuccess) return ppo_fail("ppo_carla_lane_act: hipSetDevice failed", -2);
+  hipStream_t s = l->stream;
+  // the parameters of the last update / load, and the last gae / train's reads of the storage
+  if (int rc = carla_params_wait(r->agent, s)) return rc;
+  if (hipStreamWaitEvent(s, r->sync_ev, 0) != hipSuccess) return ppo_fail("ppo_carla_lane_act: hipStreamWaitEvent failed", -2);
+  const long row = (long)step * r->E + env;
+  uint8_t* s_bev = r->bev + row * r->row_bytes;
+  float* s_meas = r->meas + row * r->NM;
+  float* s_vmeas = r->NV > 0 ? r->vmeas + row * r->NV : nullptr;
+  float* s_act = r->actions + row * r->A;
+  // :365-368 the observation row: pinned buffer (free: the previous act ended with a wait on s), one DMA
+  memcpy(l->pin, bev, (size_t)r->row_bytes);
+  if (hipMemcpyAsync(s_bev, l->pin, (size_t)r->row_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+    return ppo_fail("ppo_carla_lane_act: copy failed", -2);
+  if (lane_in(r->NM, r->NV, meas, vmeas, next_done, 0.0f, s_meas, s_vmeas, r->dones + row, nullptr, l->pin_f + r->A, s))
+    return ppo_fail("ppo_carla_lane_act: storing the measurements failed", -2);
+  // :372-379 sample on the stored row with the keys of ppo_carla_rollout_act(step, env, env + 1)
+  if (int rc = carla_forward(r->agent, l->fb, s, 1, s_bev, s_meas, s_vmeas, PPO_CARLA_SAMPLE, nullptr, env,
+                             r->iteration * r->T + step, s_act, r->logp + row, nullptr, r->values + row, nullptr,
+                             nullptr))
+    return rc;
+  if (hipMemcpyAsync(l->pin_f, s_act, (size_t)r->A * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipEventRecord(l->ev, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return ppo_fail("ppo_carla_lane_act: reading the action back failed", -2);
+  memcpy(action_host, l->pin_f, (size_t)r->A * sizeof(float));
+  return 0;
+}
+
+extern "C" int ppo_carla_lane_reward(ppo_carla_lane_t* l, int step, int env, float reward) {
+  if (!l) return ppo_fail("ppo_carla_lane_reward: null argument", -1);
+  if (int rc = lane_check(l, step, env, "ppo_carla_lane_reward")) return rc;
+  ppo_carla_rollout_t* r = l->r;
+  LaneCallGuard guard(r);
+  if (!guard.ok)
+    return ppo_fail("ppo_carla_lane_reward: called while gae, train or a lane's creation is inside the library", -1);
+  if (hipSetDevice(r->info.device) != hipSuccess) return ppo_fail("ppo_carla_lane_reward: hipSetDevice failed", -2);
+  // always within the argument block: nothing is staged
+  if (lane_in(0, 0, nullptr, nullptr, 0.0f, reward, nullptr, nullptr, nullptr, r->rewards + (long)step * r->E + env,
+              nullptr, l->stream) ||
+      hipEventRecord(l->ev, l->stream) != hipSuccess)
+    return ppo_fail("ppo_carla_lane_reward: launch failed", -2);
+  return 0;
+}
+
+extern "C" int ppo_carla_lane_sync(ppo_carla_lane_t* l) {
+  if (!l) return ppo_fail("ppo_carla_lane_sync: null argument", -1);
+  if (!l->r) return ppo_fail("ppo_carla_lane_sync: the lane's rollout object was destroyed", -1);
+  LaneCallGuard guard(l->r);
+  if (!guard.ok) return ppo_fail("ppo_carla_lane_sync: called while gae, train or a lane's creation is inside the library", -1);
+  if (hipSetDevice(l->r->info.device) != hipSuccess || hipStreamSynchronize(l->stream) != hipSuccess)
+    return ppo_fail("ppo_carla_lane_sync: synchronisation failed", -2);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // test hooks (ppo_carla.h)
 // ------------------------------------------------------------------------------------------
+extern "C" int ppo_carla_debug_lane_in(int nm, int nv, const float* meas, const float* vmeas, float next_done,
+                                       float reward, float* meas_row, float* vmeas_row, float* done_row,
+                                       float* reward_row, void* stream) {
+  if (nm < 0 || nv < 0) return ppo_fail("ppo_carla_debug_lane_in: nm and nv must be >= 0", -1);
+  if ((nm > 0 && (!meas || !meas_row)) || (nv > 0 && (!vmeas || !vmeas_row)))
+    return ppo_fail("ppo_carla_debug_lane_in: null argument", -1);
+  if (int rc = ppo_runtime_check()) return rc;
+  if (lane_in(nm, nv, meas, vmeas, next_done, reward, nm ? meas_row : nullptr, nv ? vmeas_row : nullptr, done_row,
+              reward_row, nullptr, (hipStream_t)stream) != 0 ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+    return ppo_fail("ppo_carla_debug_lane_in: launch failed", -2);
+  return 0;
+}
+
 extern "C" int ppo_carla_debug_gather(long n, long row_bytes, const void* src, const int32_t* idx, void* dst,
                                       void* stream) {
   if (!src || !idx || !dst) return ppo_fail("ppo_carla_debug_gather: null argument", -1);

@@ -277,6 +277,12 @@ SYMBOLS = [
     ("ppo_carla_rollout_set_iteration", _I, [_VP, _L]),
     ("ppo_carla_debug_gather", _I, [_L, _L, _VP, _VP, _VP, _VP]),
     ("ppo_carla_debug_gather_f32", _I, [_L, _I, C.POINTER(_VP), C.POINTER(_I), _VP, C.POINTER(_VP), _VP]),
+    ("ppo_carla_lane_create", _I, [_VP, C.POINTER(_VP)]),
+    ("ppo_carla_lane_destroy", _I, [_VP]),
+    ("ppo_carla_lane_act", _I, [_VP, _I, _I, _VP, _FP, _FP, _F, _FP]),
+    ("ppo_carla_lane_reward", _I, [_VP, _I, _I, _F]),
+    ("ppo_carla_lane_sync", _I, [_VP]),
+    ("ppo_carla_debug_lane_in", _I, [_I, _I, _FP, _FP, _F, _F, _FP, _FP, _FP, _FP, _VP]),
 ]
 
 
@@ -853,7 +859,8 @@ class CarlaAgent:
 class CarlaRollout:
     """Rollout storage, GAE and the epoch loop of the CaRL trainer (ac_ppo_carla.cpp:284-621) beside a
     CarlaAgent: ppo_carla_rollout_* of include/ppo_carla.h. Calls are serial (the agent's activation
-    buffers are shared); every array argument is a DeviceArray."""
+    buffers are shared); every array argument is a DeviceArray. lane() gives a CarlaLane, the handle of
+    one thread of a concurrent collection."""
 
     def __init__(self, agent: CarlaAgent, num_steps, num_envs, update_epochs=3, num_minibatches=4, gamma=0.99,
                  gae_lambda=0.95, seed=1, rank=0):
@@ -861,9 +868,19 @@ class CarlaRollout:
         self.cfg = CarlaRolloutConfig(num_steps, num_envs, update_epochs, num_minibatches, gamma, gae_lambda, seed,
                                       rank)
         self._h = C.c_void_p()
+        self._lanes = []
         check(lib().ppo_carla_rollout_create(agent._h, C.byref(self.cfg), C.byref(self._h)))
 
+    def lane(self) -> "CarlaLane":
+        """a new act lane (at most 64 per object): one thread's handle for concurrent collection"""
+        ln = CarlaLane(self)
+        self._lanes.append(ln)
+        return ln
+
     def close(self):
+        for ln in self._lanes:  # the lanes go before their object
+            ln.close()
+        self._lanes = []
         if self._h:
             lib().ppo_carla_rollout_destroy(self._h)
             self._h = C.c_void_p()
@@ -928,6 +945,48 @@ class CarlaRollout:
         check(lib().ppo_carla_rollout_set_iteration(self._h, int(it)))
 
 
+class CarlaLane:
+    """One act lane of a CarlaRollout (ppo_carla_lane_* of include/ppo_carla.h): a stream, a private set
+    of the forward's buffers and a pinned host buffer, for one host thread that runs one env's steps
+    while other lanes do the same for other envs (ac_ppo_carla.cpp:355-417). ctypes releases the GIL
+    during a call, so Python threads with a lane each run concurrently. Arguments are host arrays."""
+
+    def __init__(self, rollout: CarlaRollout):
+        self.rollout = rollout  # keeps the object (and its agent) alive
+        self._h = C.c_void_p()
+        self._A = rollout.agent.layout2.A
+        check(lib().ppo_carla_lane_create(rollout._h, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            check(lib().ppo_carla_lane_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def act(self, step, env, bev, meas, vmeas, next_done=0.0):
+        """stores the observation of (step, env), samples and returns the action [A] (float32)"""
+        bev = np.ascontiguousarray(bev, np.uint8)
+        meas = np.ascontiguousarray(meas, np.float32)
+        vmeas = np.ascontiguousarray(vmeas, np.float32)
+        L = self.rollout.agent.layout2
+        assert bev.size == L.C * L.IH * L.IW and meas.size == L.NM and vmeas.size == L.NV
+        out = np.empty(self._A, np.float32)
+        check(lib().ppo_carla_lane_act(self._h, step, env, bev.ctypes.data, meas.ctypes.data,
+                                       vmeas.ctypes.data if vmeas.size else None, float(next_done), out.ctypes.data))
+        return out
+
+    def reward(self, step, env, reward):
+        check(lib().ppo_carla_lane_reward(self._h, step, env, float(reward)))
+
+    def sync(self):
+        check(lib().ppo_carla_lane_sync(self._h))
+
+
 class CarlaTrainer:
     """One iteration of the reference's CaRL loop (ac_ppo_carla.cpp:332-621) against caller-supplied
     observations, mirroring Trainer: lr anneal -> T x (act, env step) -> GAE -> train. `env_step(actions)`
@@ -988,6 +1047,16 @@ def carla_gather(src: "DeviceArray", idx: "DeviceArray", dst: "DeviceArray", n, 
     """ppo_carla_debug_gather: dst[i, :] = src[idx[i], :] for n packed rows of row_bytes bytes; the byte
     offsets move the base pointers (unaligned rows)."""
     check(lib().ppo_carla_debug_gather(n, row_bytes, src.ptr + src_offset, idx.ptr, dst.ptr + dst_offset, None))
+
+
+def carla_lane_in(meas, vmeas, next_done, reward, meas_row=None, vmeas_row=None, done_row=None, reward_row=None):
+    """ppo_carla_debug_lane_in: a lane's small fp32 inputs (host values) into device rows; the rows are
+    device addresses (int) or None to skip one"""
+    meas = np.ascontiguousarray(meas, np.float32)
+    vmeas = np.ascontiguousarray(vmeas, np.float32)
+    check(lib().ppo_carla_debug_lane_in(meas.size, vmeas.size, meas.ctypes.data if meas.size else None,
+                                        vmeas.ctypes.data if vmeas.size else None, float(next_done), float(reward),
+                                        meas_row, vmeas_row, done_row, reward_row, None))
 
 
 def carla_gather_f32(srcs, idx: "DeviceArray", dsts, n, widths):
