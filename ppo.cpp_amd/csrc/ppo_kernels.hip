@@ -21,10 +21,8 @@
 #include <cstdlib>
 #include <type_traits>
 // cache policy of k_dw_dma's read-once streams (the two-phase dW of wide inputs, e.g. Ant): 0 default,
-// 2 non-temporal (A/B)
-#ifndef PPO_DWD_AUX
-#define PPO_DWD_AUX 0
-#endif
+// 2 non-temporal
+constexpr int kDwdAux = 0;
 
 // =============================================================================================
 // k_act
@@ -925,13 +923,13 @@ PPO_DEV void dw_phase_dma(const float* __restrict__ DZ, const float* __restrict_
         const long row = mb + i / (NO / 256);
         const uint32_t voff = row < m1 ? (uint32_t)(((long)i * 256 + mb * NO) * 4 + lane * 16) : 0xFFFFFFF0u;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(bdz.r, (__attribute__((address_space(3))) void*)(b + i * 256), 16,
-                                                 voff, 0, 0, PPO_DWD_AUX);
+                                                 voff, 0, 0, kDwdAux);
       } else if (i < NT) {
         const int e = (i - ND) * 256 + lane * 4;  // float of the stage's IN block
         const long row = mb + e / LDI;
         const uint32_t voff = row < m1 ? (uint32_t)((mb * LDI + e) * 4) : 0xFFFFFFF0u;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(bin.r, (__attribute__((address_space(3))) void*)(b + ADZ + (i - ND) * 256),
-                                                 16, voff, 0, 0, PPO_DWD_AUX);
+                                                 16, voff, 0, 0, kDwdAux);
       }
     }
   };
@@ -1288,20 +1286,7 @@ __global__ __launch_bounds__(512) void k_dwf_dma(DwArgs a) {
 // instead of 1 KB (the hand-off's H1 third).
 // cache policy of k_dwf_bx's hand-off stream (read once): 2 non-temporal (dW 3.41 -> 3.31 ms per metric
 // iteration, bitwise the same; profiles/r06/dw_nt/), 0 the default policy
-#ifndef PPO_DW_AUX
-#define PPO_DW_AUX 2
-#endif
-// k_dwf_bx's split-K partials (read once by k_colsum): PPO_DW_NTST = 1 stores them non-temporal (A/B)
-#ifndef PPO_DW_NTST
-#define PPO_DW_NTST 0
-#endif
-PPO_DEV void dw_st(float* p, float v) {
-#if PPO_DW_NTST
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+constexpr int kDwAux = 2;
 template <int H, int OP, bool RC>
 struct DwbxGeo {
   static constexpr int KS = 16, LDH = H, LDX = OP;
@@ -1384,7 +1369,7 @@ __global__ __launch_bounds__(512) void k_dwf_bx(DwArgs a) {
         const uint32_t voff = row < m1 ? (uint32_t)((row * H) * 4 + lane * 16) : 0xFFFFFFF0u;
         __builtin_amdgcn_raw_ptr_buffer_load_lds((s3 == 0 ? bdz2 : s3 == 1 ? bh1 : bdz1).r,
                                                  (__attribute__((address_space(3))) void*)(b + dst + r * LDH), 16,
-                                                 voff, 0, 0, PPO_DW_AUX);
+                                                 voff, 0, 0, kDwAux);
       }
     }
     if (RC && wave == 7) {  // the stage's 16 rows x (mean, 1 / std): 32 dwords (lanes 32..63 zero-fill the pad)
@@ -1398,7 +1383,7 @@ __global__ __launch_bounds__(512) void k_dwf_bx(DwArgs a) {
       const long row = mb + r;
       const uint32_t voff = row < m1 ? (uint32_t)((row * OP + (e - r * OP)) * 4) : 0xFFFFFFF0u;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(bxn.r, (__attribute__((address_space(3))) void*)(b + oXN + wave * 256), 16,
-                                               voff, 0, 0, PPO_DW_AUX);
+                                               voff, 0, 0, kDwAux);
     }
   };
   const bool xw = wave < NXI;
@@ -1501,8 +1486,8 @@ __global__ __launch_bounds__(512) void k_dwf_bx(DwArgs a) {
     for (int u = 0; u < TOW; ++u)
 #pragma unroll
       for (int v = 0; v < TIW; ++v)
-        dw_st(out + (size_t)(obase + (wo * TOW + u) * 32 + orow) * H + (wi * TIW + v) * 32 + l32, acc[u][v][r]);
-    if (w1_wave && l32 < OP) dw_st(out + (size_t)H * H + (size_t)(w1row + orow) * OP + l32, acc1[r]);
+        *(out + (size_t)(obase + (wo * TOW + u) * 32 + orow) * H + (wi * TIW + v) * 32 + l32) = acc[u][v][r];
+    if (w1_wave && l32 < OP) *(out + (size_t)H * H + (size_t)(w1row + orow) * OP + l32) = acc1[r];
   }
 }
 
@@ -1533,24 +1518,6 @@ struct DwsoGeo {
   static constexpr int SPILL = 2 * XPIECE + 64 * 8;  // behind the images: where the waves without an Xn share store
   static constexpr int lds = total + SPILL;
 };
-// A/B switches of k_dwf_so's stage loop (profiles/r07/dw_split_once/): PPO_DWSO_SGB = 1 places a quarter of the
-// next stage's split and stores and the next H1 operand's reads between the 12 MFMAs of each H1 column block
-// with sched_group_barrier, fenced per block (0: the compiler's own order, which splits in clumps between the
-// blocks: dW 3.22 -> 3.00 ms per metric iteration, with SGB 2.80-2.98). Unfenced, the pattern pulled the splits
-// in front of the stage's first MFMA, onto the wait for the loads: slower than k_dwf_bx.
-// PPO_DWSO_RELOAD = 1 reloads a source's registers right after their split (a full stage in flight) instead of
-// at the stage's end: dW 2.8-2.9 ms, but on one of three boxes k_upd ran 4 % slower beside it and the iteration
-// no faster than k_dwf_bx's; 0 won on every box. PPO_DWSO_PRIO = 1 raises the priority of waves 4..7 (one of
-// the two waves of every SIMD): no change.
-#ifndef PPO_DWSO_SGB
-#define PPO_DWSO_SGB 1
-#endif
-#ifndef PPO_DWSO_PRIO
-#define PPO_DWSO_PRIO 0
-#endif
-#ifndef PPO_DWSO_RELOAD
-#define PPO_DWSO_RELOAD 0
-#endif
 typedef short dwso_v4s __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 PPO_DEV u32x2 lds_read_tr16(const unsigned char* p) {
@@ -1621,12 +1588,12 @@ __global__ __launch_bounds__(512) void k_dwf_so(DwArgs a) {
       for (int i = 0; i < 2; ++i) {
         const uint32_t voff = row < m1 ? (uint32_t)((row * H + scol + 128 * i) * 4) : 0xFFFFFFF0u;
         pv[2 * s3 + i] = __builtin_bit_cast(
-            f4, __builtin_amdgcn_raw_buffer_load_b128((s3 == 0 ? bdz2 : s3 == 1 ? bh1 : bdz1).r, voff, 0, PPO_DW_AUX));
+            f4, __builtin_amdgcn_raw_buffer_load_b128((s3 == 0 ? bdz2 : s3 == 1 ? bh1 : bdz1).r, voff, 0, kDwAux));
       }
     } else {  // (the other waves: out of range, no memory access, zeros)
       const long xr = mb + xrow;
       const uint32_t voff = xw && xr < m1 ? (uint32_t)((xr * OP + xcol) * 4) : 0xFFFFFFF0u;
-      px = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(bxn.r, voff, 0, PPO_DW_AUX));
+      px = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(bxn.r, voff, 0, kDwAux));
     }
   };
   auto load = [&](long mb) {
@@ -1664,9 +1631,6 @@ __global__ __launch_bounds__(512) void k_dwf_so(DwArgs a) {
     lds_barrier();
   }
   const int nst = (int)((m1 - m0 + KS - 1) / KS);
-#if PPO_DWSO_PRIO
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   // prologue: stage 0 into image 0, stage 1 into the registers. Stages past the last load zeros and are
   // never read.
   load(m0);
@@ -1693,12 +1657,12 @@ __global__ __launch_bounds__(512) void k_dwf_so(DwArgs a) {
     }
     const int cb = GE::SRC + dwso_off(0, wi * TIW * 32);  // (TIW = 4 column blocks: 512 bytes apart)
     const long mb2 = m0 + (long)(sI + 2) * KS;  // the stage whose loads replace the registers just split
-#if PPO_DWSO_SGB
     Split3 bs = dwso_operand<GE::PIECE>(ib + cb + rofs0, ib + cb + rofs1);
 #pragma unroll
     for (int v = 0; v < TIW; ++v) {
       // the H1 operand of block v + 1 is read, and a quarter of stage sI + 1 split and stored, between this
-      // block's MFMAs: per MFMA its share of the VALU and LDS instructions (fenced per block)
+      // block's MFMAs: per MFMA its share of the VALU and LDS instructions, fenced per block (unfenced, the
+      // pattern pulled the splits in front of the stage's first MFMA, onto the wait for the loads)
       __builtin_amdgcn_sched_barrier(0);
       Split3 bn = bs;
       if (v + 1 < TIW) bn = dwso_operand<GE::PIECE>(ib + cb + 512 * (v + 1) + rofs0, ib + cb + 512 * (v + 1) + rofs1);
@@ -1714,19 +1678,8 @@ __global__ __launch_bounds__(512) void k_dwf_so(DwArgs a) {
         __builtin_amdgcn_sched_group_barrier(0x080, (12 + NM - 1) / NM, 0);  // its LDS reads / stores
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (PPO_DWSO_RELOAD) load_src(mb2, v);
     }
-#else
-#pragma unroll
-    for (int v = 0; v < TIW; ++v) {
-      const Split3 bs = dwso_operand<GE::PIECE>(ib + cb + 512 * v + rofs0, ib + cb + 512 * v + rofs1);
-#pragma unroll
-      for (int u = 0; u < TOW; ++u) acc[u][v] = mfma_split<NP>(as[u], bs, acc[u][v]);
-      put(ob, v);
-      if (PPO_DWSO_RELOAD) load_src(mb2, v);
-    }
-#endif
-    if (!PPO_DWSO_RELOAD) load(mb2);
+    load(mb2);
     lds_barrier();
   }
   float* out = a.slab[trunk] + (size_t)blockIdx.x * a.slab_stride;
@@ -1737,8 +1690,8 @@ __global__ __launch_bounds__(512) void k_dwf_so(DwArgs a) {
     for (int u = 0; u < TOW; ++u)
 #pragma unroll
       for (int v = 0; v < TIW; ++v)
-        dw_st(out + (size_t)(obase + (wo * TOW + u) * 32 + orow) * H + (wi * TIW + v) * 32 + l32, acc[u][v][r]);
-    if (w1_wave && l32 < OP) dw_st(out + (size_t)H * H + (size_t)(w1row + orow) * OP + l32, acc1[r]);
+        *(out + (size_t)(obase + (wo * TOW + u) * 32 + orow) * H + (wi * TIW + v) * 32 + l32) = acc[u][v][r];
+    if (w1_wave && l32 < OP) *(out + (size_t)H * H + (size_t)(w1row + orow) * OP + l32) = acc1[r];
   }
 }
 
@@ -1788,17 +1741,6 @@ PPO_DEV void colsum_fold(const ColsumArgs& a, int sgi, int b, float ss) {
   if (lane == 0) __hip_atomic_store((gu32*)(a.cnt + sgi), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// split-K partials are read once: PPO_CS_NT = 1 loads them non-temporal (A/B)
-#ifndef PPO_CS_NT
-#define PPO_CS_NT 0
-#endif
-PPO_DEV f4 cs_ld4(const float* p) {
-#if PPO_CS_NT
-  return __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-#else
-  return ld4(p);
-#endif
-}
 __global__ __launch_bounds__(256) void k_colsum(ColsumArgs a) {
   __shared__ f4 part[16][16];
   const int b = blockIdx.x;
@@ -1817,10 +1759,10 @@ __global__ __launch_bounds__(256) void k_colsum(ColsumArgs a) {
       // eight loads in flight (one round trip for the usual 128 chunks); each accumulator still
       // takes its rows in the order of the four-wide loop below, so the sums are unchanged
       for (; r + 112 < S.count; r += 128) {
-        const f4 x0 = cs_ld4(src + (size_t)r * S.stride), x1 = cs_ld4(src + (size_t)(r + 16) * S.stride);
-        const f4 x2 = cs_ld4(src + (size_t)(r + 32) * S.stride), x3 = cs_ld4(src + (size_t)(r + 48) * S.stride);
-        const f4 x4 = cs_ld4(src + (size_t)(r + 64) * S.stride), x5 = cs_ld4(src + (size_t)(r + 80) * S.stride);
-        const f4 x6 = cs_ld4(src + (size_t)(r + 96) * S.stride), x7 = cs_ld4(src + (size_t)(r + 112) * S.stride);
+        const f4 x0 = ld4(src + (size_t)r * S.stride), x1 = ld4(src + (size_t)(r + 16) * S.stride);
+        const f4 x2 = ld4(src + (size_t)(r + 32) * S.stride), x3 = ld4(src + (size_t)(r + 48) * S.stride);
+        const f4 x4 = ld4(src + (size_t)(r + 64) * S.stride), x5 = ld4(src + (size_t)(r + 80) * S.stride);
+        const f4 x6 = ld4(src + (size_t)(r + 96) * S.stride), x7 = ld4(src + (size_t)(r + 112) * S.stride);
         acc0 += x0;
         acc1 += x1;
         acc2 += x2;
@@ -1831,12 +1773,12 @@ __global__ __launch_bounds__(256) void k_colsum(ColsumArgs a) {
         acc3 += x7;
       }
       for (; r + 48 < S.count; r += 64) {
-        acc0 += cs_ld4(src + (size_t)r * S.stride);
-        acc1 += cs_ld4(src + (size_t)(r + 16) * S.stride);
-        acc2 += cs_ld4(src + (size_t)(r + 32) * S.stride);
-        acc3 += cs_ld4(src + (size_t)(r + 48) * S.stride);
+        acc0 += ld4(src + (size_t)r * S.stride);
+        acc1 += ld4(src + (size_t)(r + 16) * S.stride);
+        acc2 += ld4(src + (size_t)(r + 32) * S.stride);
+        acc3 += ld4(src + (size_t)(r + 48) * S.stride);
       }
-      for (; r < S.count; r += 16) acc0 += cs_ld4(src + (size_t)r * S.stride);
+      for (; r < S.count; r += 16) acc0 += ld4(src + (size_t)r * S.stride);
     }
     part[q][c] = (acc0 + acc1) + (acc2 + acc3);
     __syncthreads();

@@ -28,59 +28,6 @@
 #include <cstdlib>
 #include "ppo_kernels.hpp"
 
-// 1: a tile's gathered rows are committed to LDS by the previous tile (EARLY in upd16_body); 0: at the
-// tile top (A/B builds)
-#ifndef PPO_UPD_EARLY
-#define PPO_UPD_EARLY 0
-#endif
-// A/B switches of round-6 k_upd changes (each 1 = on; all off = the round-5 kernel): merged
-// LayerNorm statistics (one exchange per LayerNorm), the two barriers other exchange barriers cover,
-// head partials summed inside the loss, branch-free prefetch loads, no LDS copy of the critic's h2,
-// the tile top's first barrier (covered by the previous tile's layer-1 backward exchange), the next
-// tile's rows committed in the layer-1 backward (EARLY). Measured per launch against all-off
-// (profiles/r06/kupd_ab/): EARLY +9.6 %, BF +1.4 %; CHAN -1.0 %, BAR -1.0 %, PRE -0.5 %, CH2 0 one at
-// a time on one box, but CHAN + BAR + PRE + CH2 together +1.2 % and with TOP +1.5 % on another (the
-// critic's tile 75 K -> 67 K cycles, the actor's 79 K -> 81 K: the launch is the actor's, and the
-// critic's shorter phases leave the actor's loss with fewer partner MFMA gaps). Not kept: all off.
-// 1: the H1 / DZ2 hand-off rows are stored from inside the next GEMM (read back from the LDS pieces,
-// issued after its first weight prefetches) instead of from registers before it (A/B builds). Measured
-// +11 % per launch (spills 31 -> 53, profiles/r06/kupd_defer/): off
-#ifndef PPO_UPD_DEFER
-#define PPO_UPD_DEFER 0
-#endif
-// 1: the head weights (NHT = 1) held in registers from the tile top (16 VGPRs); 0: loaded at each use.
-// Measured 0: k_upd 0.610 -> 0.602 ms per launch (spills 31 -> 28; results bitwise equal, profiles/r06/kupd_hwb/)
-#ifndef PPO_V_HWB
-#define PPO_V_HWB 0
-#endif
-// 1: the next tile's permutation entries requested after the layer-2 GEMM and its rows after the dh1 GEMM
-// (shorter register live ranges), 0: at the tile top and after the layer-2 GEMM (A/B)
-// 1: no register prefetch of the next tile's rows (each tile gathers its rows at its top; A/B)
-#ifndef PPO_V_NOPREF
-#define PPO_V_NOPREF 0
-#endif
-#ifndef PPO_V_PLATE
-#define PPO_V_PLATE 0
-#endif
-#ifndef PPO_V_CHAN
-#define PPO_V_CHAN 0
-#endif
-#ifndef PPO_V_BAR
-#define PPO_V_BAR 0
-#endif
-#ifndef PPO_V_PRE
-#define PPO_V_PRE 0
-#endif
-#ifndef PPO_V_BF
-#define PPO_V_BF 0
-#endif
-#ifndef PPO_V_TOP
-#define PPO_V_TOP 0
-#endif
-#ifndef PPO_V_CH2
-#define PPO_V_CH2 0
-#endif
-
 #ifdef PPO_STAMPS
 // diagnostic build only: per-wave shader-clock stamps at phase ends of the first 16 tiles of every workgroup
 #define PPO_NSTAMP 13
@@ -226,21 +173,12 @@ PPO_DEV void mm_fr(f4 (&out)[FT][RT], PBuf wb, int wlane, const float* in) {
 // A pieces stream through a ring of NS units (D = NS - 1 ahead, ~ one 32-k block of every feature tile).
 // weight-piece ring depth (32-k units in flight ahead): 2 / 3 / 4 / 5 measured 0.62 / 0.61 / 0.65 /
 // 0.69 ms per launch (deeper rings spill; profiles/r05/bx6/abm2, abm3)
-#ifndef PPO_BX_RING
-#define PPO_BX_RING 3
-#endif
-constexpr int kBxRing = PPO_BX_RING;
+constexpr int kBxRing = 3;
 PPO_DEV u32x4 pld4u(PBuf b, int lane_floats, int uni_floats) { return __builtin_bit_cast(u32x4, pld4(b, lane_floats, uni_floats)); }
 // diag_unit0 (stamps build, timing only): every weight unit read from the wave's first unit, so the
 // wave streams 3 KB from the L1 instead of 96 KB from L2 (is the weight stream the GEMMs' bound?)
-struct NoMid {
-  PPO_DEV void operator()() const {}
-};
-// mid (PPO_UPD_DEFER): called once, right after the first in-loop weight prefetch — vector-memory work
-// (the hand-off stores) issued there is older than only the weight loads of units D + 1 .., so the
-// wave first waits on it D + 1 units later instead of at the GEMM's first unit
-template <int FT, int RT, int NKB, int LDB, class Mid = NoMid>
-PPO_DEV void mm_bx(f4 (&out)[FT][RT], PBuf wb, int wlane, const float* inb, bool diag_unit0 = false, Mid mid = Mid{}) {
+template <int FT, int RT, int NKB, int LDB>
+PPO_DEV void mm_bx(f4 (&out)[FT][RT], PBuf wb, int wlane, const float* inb, bool diag_unit0 = false) {
   static_assert(NKB % 2 == 0, "mm_bx: 32-wide k blocks");
   constexpr int NKK = NKB / 2, U = NKK * FT, D = kBxRing, NS = D + 1, PS = 8 * NKB;
   u32x4 ar[NS][3];
@@ -267,7 +205,6 @@ PPO_DEV void mm_bx(f4 (&out)[FT][RT], PBuf wb, int wlane, const float* inb, bool
     for (int ft = 0; ft < FT; ++ft) {
       const int u = kk * FT + ft;
       if (u + D < U) load_unit(u + D, ar[(u + D) % NS]);
-      if (u == 0) mid();
       // pin the prefetch here: the scheduler otherwise sinks it next to its use
       __builtin_amdgcn_sched_barrier(0);
       const u32x4(&av)[3] = ar[u % NS];
@@ -303,37 +240,6 @@ PPO_DEV void lds_store_pieces(float* actb, const f4 (&v)[FT][RT], int rbase, int
       *reinterpret_cast<u32x2*>(q + PS) = u32x2{m0, m1};
       *reinterpret_cast<u32x2*>(q + 2 * PS) = u32x2{l0, l1};
     }
-}
-
-// the hand-off rows store_tile_rows writes, read back from lds_store_pieces' split-bf16 pieces:
-// x = hi + (mid + lo) exactly (hi, mid, lo are consecutive 8-bit slices of x's significand), so the
-// bytes are store_tile_rows' (a -0 comes back as +0)
-template <int FT, int RT, int LDB, int PS>
-PPO_DEV void store_rows_from_pieces(float* __restrict__ dst, int ld, const float* actb, int m0, int M, int rbase,
-                                    int fbase, int j, int g) {
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    const int m = m0 + rbase + 16 * rt + j;
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) {
-      const int f0 = fbase + 16 * ft;
-      const float* q = actb + (rbase + 16 * rt + j) * LDB + 16 * (f0 >> 5) + 4 * g + 2 * ((f0 >> 4) & 1);
-      const u32x2 h = *reinterpret_cast<const u32x2*>(q);
-      const u32x2 md = *reinterpret_cast<const u32x2*>(q + PS);
-      const u32x2 lo = *reinterpret_cast<const u32x2*>(q + 2 * PS);
-      f4 v;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int w = r >> 1, sh = (r & 1) ? 0 : 16;
-        const float fh = __uint_as_float(((h[w] << sh) & 0xffff0000u));
-        const float fm = __uint_as_float(((md[w] << sh) & 0xffff0000u));
-        const float fl = __uint_as_float(((lo[w] << sh) & 0xffff0000u));
-        v[r] = fh + (fm + fl);
-      }
-      if (m < M) st4(dst + (size_t)m * ld + f0 + 4 * g, v);
-    }
-  }
 }
 
 // bias init: out[ft][rt] = b[fbase + 16 ft + 4 g + r]
@@ -407,102 +313,39 @@ PPO_DEV void rows_total2(float (&s)[RT], float (&q)[RT], float* red0, float* red
   }
 }
 
-// LayerNorm statistics of z (eps 1e-5, biased variance as torch::layer_norm). One wave holds H / WF
-// features of a row: it computes their sum and their squared deviations about its OWN mean (two-pass
-// within the wave), and the WF waves' (sum, M2) pairs are merged after ONE cross-wave exchange with
-// Chan's parallel formula, M2 = sum_w M2_w + n_w (mean_w - mean)^2 (exactly the two-pass variance in
-// exact arithmetic, as stable in fp32): one barrier per LayerNorm instead of two. WF = 1 is the plain
-// two-pass form.
+// LayerNorm statistics of z (eps 1e-5, biased variance as torch::layer_norm), two-pass: the row sums
+// over all H features give the mean, then the squared deviations about that mean give the variance.
+// Each pass is summed across the WF feature-group waves by rows_total (red0, then red1), so a
+// LayerNorm over several waves takes two cross-wave exchanges (two barriers); WF = 1 takes none.
 template <int FT, int RT, int WF, int R, int H>
 PPO_DEV void ln_rows(const f4 (&z)[FT][RT], float (&mu)[RT], float (&rs)[RT], float* red0, float* red1, int wf,
                      int rbase, int j, int g) {
   constexpr float invH = 1.0f / H;
-#if !PPO_V_CHAN
-  {
-    float s[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      float t = 0.f;
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft) t += (z[ft][rt].x + z[ft][rt].y) + (z[ft][rt].z + z[ft][rt].w);
-      s[rt] = t;
-    }
-    rows_total<WF, RT, R>(s, red0, wf, rbase, j, g);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      mu[rt] = s[rt] * invH;
-      float t = 0.f;
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float d = z[ft][rt][r] - mu[rt];
-          t += d * d;
-        }
-      s[rt] = t;
-    }
-    rows_total<WF, RT, R>(s, red1, wf, rbase, j, g);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) rs[rt] = 1.0f / sqrtf(s[rt] * invH + 1e-5f);
-    return;
-  }
-#endif
-  constexpr int HW = H / WF;
-  constexpr float invW = 1.0f / HW;
-  float s[RT], q[RT];
+  float s[RT];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     float t = 0.f;
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) t += (z[ft][rt].x + z[ft][rt].y) + (z[ft][rt].z + z[ft][rt].w);
-    s[rt] = row_allreduce(t);
+    s[rt] = t;
   }
+  rows_total<WF, RT, R>(s, red0, wf, rbase, j, g);
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
-    const float mw = s[rt] * invW;
+    mu[rt] = s[rt] * invH;
     float t = 0.f;
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float d = z[ft][rt][r] - mw;
+        const float d = z[ft][rt][r] - mu[rt];
         t += d * d;
       }
-    q[rt] = row_allreduce(t);
+    s[rt] = t;
   }
-  if constexpr (WF > 1) {
-    if (g == 0) {
+  rows_total<WF, RT, R>(s, red1, wf, rbase, j, g);
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        red0[wf * R + rbase + 16 * rt + j] = s[rt];
-        red1[wf * R + rbase + 16 * rt + j] = q[rt];
-      }
-    }
-    lds_barrier();
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      float sw[WF], tot = 0.f;
-#pragma unroll
-      for (int w = 0; w < WF; ++w) {
-        sw[w] = red0[w * R + rbase + 16 * rt + j];
-        tot += sw[w];
-      }
-      mu[rt] = tot * invH;
-      float m2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < WF; ++w) {
-        const float dm = sw[w] * invW - mu[rt];
-        m2 += red1[w * R + rbase + 16 * rt + j] + (float)HW * (dm * dm);
-      }
-      rs[rt] = 1.0f / sqrtf(m2 * invH + 1e-5f);
-    }
-  } else {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      mu[rt] = s[rt] * invH;
-      rs[rt] = 1.0f / sqrtf(q[rt] * invH + 1e-5f);
-    }
-  }
+  for (int rt = 0; rt < RT; ++rt) rs[rt] = 1.0f / sqrtf(s[rt] * invH + 1e-5f);
 }
 
 template <int CTRL, int LEN, int M>
@@ -571,10 +414,6 @@ PPO_DEV void col_sums(Fn v, float* acc, int fbase, int j, int g) {
   acc[fbase + 16 * (j >> 2) + 4 * g + (j & 3)] += x[0];
 }
 
-// PPO_UPD_NT (A/B): the hand-off rows (H1 / DZ2 / DZ1) as non-temporal stores
-#ifndef PPO_UPD_NT
-#define PPO_UPD_NT 0
-#endif
 template <int FT, int RT>
 PPO_DEV void store_tile_rows(float* __restrict__ dst, int ld, const f4 (&v)[FT][RT], int m0, int M, int rbase,
                              int fbase, int j, int g, bool diag_blocked = false) {
@@ -599,13 +438,7 @@ PPO_DEV void store_tile_rows(float* __restrict__ dst, int ld, const f4 (&v)[FT][
     const int m = m0 + rbase + 16 * rt + j;
     if (m < M) {
 #pragma unroll
-      for (int ft = 0; ft < FT; ++ft) {
-#if PPO_UPD_NT
-        __builtin_nontemporal_store(v[ft][rt], reinterpret_cast<f4*>(dst + (size_t)m * ld + fbase + 16 * ft + 4 * g));
-#else
-        st4(dst + (size_t)m * ld + fbase + 16 * ft + 4 * g, v[ft][rt]);
-#endif
-      }
+      for (int ft = 0; ft < FT; ++ft) st4(dst + (size_t)m * ld + fbase + 16 * ft + 4 * g, v[ft][rt]);
     }
   }
 }
@@ -638,8 +471,8 @@ PPO_DEV int head_bias(const PackedLayout& K, int trunk, int h) {
 // The PPO loss of one tile and its gradient wrt the head pre-activations: PRE -> GG (critic: the
 // clipped value loss, ppo:520-533; actor: Beta or Normal log-prob / entropy, the clipped surrogate,
 // ppo:497-519, ac:815-875), the per-lane loss statistics added to lst. Shared by k_upd and k_upd32.
-// pre(row, h): a head pre-activation for the critic and the one-row-per-8-lanes Beta loss (k_upd sums the
-// head partials there directly); the other losses read the materialised PRE array.
+// pre(row, h): a head pre-activation for the critic and the one-row-per-8-lanes Beta loss; the other
+// losses index the materialised PRE array directly.
 template <bool LN, int R, int ITS, int LDG, typename PreFn>
 PPO_DEV void upd_loss(const UpdArgs& a, int trunk, int tid, int m0, float c, float adv_mean, float adv_std,
                       PreFn pre, const float* PRE, float* GG, float* ROWS, const float* ACTN, float* ITM,
@@ -912,60 +745,11 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
   // Gather prefetch, two stages one tile ahead: permutation indices at the top of a tile, the
   // rows' data after its forward pass; committed to LDS at the top of the next tile.
   // (register-staged only for narrow inputs; wide ones (O > 32) gather synchronously)
-  constexpr bool PREF = (R * OP + 255) / 256 <= 4 && !PPO_V_NOPREF;
+  constexpr bool PREF = (R * OP + 255) / 256 <= 4;
   constexpr int NG = PREF ? (R * OP + 255) / 256 : 1;   // gather items per thread
   constexpr int NAI = PREF ? (R * PPO_UPD_MAXA + 255) / 256 : 1;  // action items per thread
   int pg[NG], pra, pac[NAI];
   float vg[NG], vr1 = 0.f, vr2 = 0.f, vac[NAI];
-#if PPO_V_BF
-  // every load is unconditional from a clamped (valid) address and masked by a select afterwards: a
-  // load under a per-lane branch gets its own branch and, at the loop head, a vmcnt(0) wait
-  auto pref_idx = [&](int itn) {
-    const int mb = itn * R;
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int idx = tid + 256 * k, row = idx / OP, f = idx - row * OP, m = mb + row;
-      const bool ok = itn < ntiles && idx < R * OP && m < a.M && f < O;
-      const int pv = a.perm[ok ? m : 0];
-      pg[k] = ok ? pv : -1;
-    }
-    {
-      const bool ok = itn < ntiles && tid < R && mb + tid < a.M;
-      const int pv = a.perm[ok ? mb + tid : 0];
-      pra = ok ? pv : -1;
-    }
-#pragma unroll
-    for (int k = 0; k < NAI; ++k) {
-      const int idx = tid + 256 * k, row = idx / (A > 0 ? A : 1), m = mb + row;
-      const bool ok = trunk == 1 && itn < ntiles && idx < R * A && m < a.M;
-      const int pv = a.perm[ok ? m : 0];
-      pac[k] = ok ? pv : -1;
-    }
-  };
-  auto pref_data = [&](int itn) {
-    (void)itn;
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int idx = tid + 256 * k, row = idx / OP, f = idx - row * OP;
-      (void)row;
-      const float v = a.obs[(long)(pg[k] >= 0 ? pg[k] : 0) * O + (f < O ? f : 0)];
-      vg[k] = pg[k] >= 0 ? v : 0.f;
-    }
-    {
-      const int pr = pra >= 0 ? pra : 0;
-      const float x1 = trunk == 0 ? a.ret[pr] : a.logp[pr];
-      const float x2 = trunk == 0 ? a.val[pr] : a.adv[pr];
-      vr1 = pra >= 0 ? x1 : 0.f;
-      vr2 = pra >= 0 ? x2 : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < NAI; ++k) {
-      const int idx = tid + 256 * k, ai = idx - (idx / (A > 0 ? A : 1)) * A;
-      const float v = a.actions[(long)(pac[k] >= 0 ? pac[k] : 0) * A + ai];
-      vac[k] = pac[k] >= 0 ? v : 0.f;
-    }
-  };
-#else
   auto pref_idx = [&](int itn) {
     const int mb = itn * R;
 #pragma unroll
@@ -1001,7 +785,6 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
       vac[k] = pac[k] >= 0 ? a.actions[(long)pac[k] * A + ai] : 0.f;
     }
   };
-#endif
   auto commit = [&](int itc) {
     const int mb = itc * R;
 #pragma unroll
@@ -1111,20 +894,6 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
     SPAR[i] = x;
   }
   if constexpr (PREF) pref_data(blockIdx.x);
-  // EARLY (narrow inputs, LayerNorm trunks over several waves): a tile's gathered rows are committed to
-  // LDS by the PREVIOUS tile, right after its layer-1 backward exchange barrier (every wave is past its
-  // last XN / ROWS / ACTN read of that tile by then), so the tile top is one barrier and a few loads;
-  // the first tile's rows are committed here
-  constexpr bool EARLY = PPO_UPD_EARLY && PREF && LN && WF > 1;
-  constexpr bool DEFER = PPO_UPD_DEFER != 0;
-  if constexpr (EARLY) {
-    lds_barrier();  // SPAR (observation mean / std) is staged
-    commit(blockIdx.x);
-  }
-  // TOP: the tile top writes XN / ROWS / ACTN without a barrier first: the previous tile's last readers
-  // of them (layer-1 recompute, loss) all precede its layer-1 backward exchange barrier (rows_total2)
-  constexpr bool TOP = PPO_V_TOP && !EARLY && PREF && LN && WF > 1;
-  if constexpr (TOP) lds_barrier();  // SPAR (observation mean / std) is staged for the first commit
   // wide inputs: row tid's permutation entry of the next tile (clamped, as the gather clamps rows)
   int nperm = 0;
   if constexpr (!PREF) nperm = tid < R ? a.perm[min((int)blockIdx.x * R + tid, a.M - 1)] : 0;
@@ -1135,40 +904,15 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
     PPO_STAMP_START();
     if constexpr (!PREF)
       if (tid < R) ROWS[tid * 8] = __int_as_float(nperm);  // slot 0 is read only by gather_sync
-    if constexpr (!TOP) lds_barrier();  // the previous iteration's LDS readers are done (EARLY: rows committed)
-    if constexpr (EARLY) {
-      pref_idx(it + gridDim.x);
-    } else if constexpr (PREF) {
+    lds_barrier();  // the previous iteration's LDS readers are done
+    if constexpr (PREF) {
       commit(it);
-      if constexpr (!PPO_V_PLATE) pref_idx(it + gridDim.x);
+      pref_idx(it + gridDim.x);
     } else {
       if (tid < R) nperm = a.perm[min((it + (int)gridDim.x) * R + tid, a.M - 1)];
       gather_sync(it);
     }
-    // one head tile (NHT == 1): its weights, in the layout the head backward reads them (critic: w3
-    // features 4 g + r, which the forward dot product uses too; actor: heads 4 g + r of feature j),
-    // are requested here, a whole forward pass before their first use, instead of in the head
-    // phases (where they were the only loads a wave waited on outside the matrix phases)
-    f4 hwb[FT];
-    if constexpr (NHT == 1 && PPO_V_HWB) {
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft) {
-        if (trunk == 0) {
-          hwb[ft] = pld4(pb, K.cW3 + fbase + 4 * g, 16 * ft);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-#if PPO_V_BF
-            const float v = bld1(pb, (hrow_b[0][r] >= 0 ? hrow_b[0][r] : 0) + fbase + j, 16 * ft);
-            hwb[ft][r] = hrow_b[0][r] >= 0 ? v : 0.0f;
-#else
-            hwb[ft][r] = hrow_b[0][r] >= 0 ? bld1(pb, hrow_b[0][r] + fbase + j, 16 * ft) : 0.0f;
-#endif
-          }
-        }
-      }
-    }
-    if constexpr (!EARLY) lds_barrier();
+    lds_barrier();
     PPO_STAMP(0);
 
     // ---------------- layer 1 ----------------
@@ -1211,7 +955,7 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
           }
         }
       }
-    } else if (!PPO_DIAG_SKIP(4) && !(DEFER && BX)) {
+    } else if (!PPO_DIAG_SKIP(4)) {
       store_tile_rows<FT, RT>(a.H1[trunk], H, z, m0, a.M, rbase, fbase, j, g, PPO_DIAG_SKIP(14));
     }
     if constexpr (BX) lds_store_pieces<FT, RT, LDB, H / 2>(ACT, z, rbase, fbase, j, g);
@@ -1222,19 +966,13 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
     // ---------------- layer 2 ----------------
     f4 x2[FT][RT];  // LN: x_hat2; tanh: h2
     init_bias<FT, RT>(x2, pb, T.b2 + fbase + 4 * g);
-    if constexpr (BX && DEFER) {
-      const bool st_h1 = !a.h1_skip && !PPO_DIAG_SKIP(4);
-      mm_bx<FT, RT, NT, LDB>(x2, wbx, w2blane, actb_in, PPO_DIAG_SKIP(13), [&]() {
-        if (st_h1) store_rows_from_pieces<FT, RT, LDB, H / 2>(a.H1[trunk], H, ACT, m0, a.M, rbase, fbase, j, g);
-      });
-    } else if constexpr (BX) {
+    if constexpr (BX) {
       mm_bx<FT, RT, NT, LDB>(x2, wbx, w2blane, actb_in, PPO_DIAG_SKIP(13));
     } else {
       mm_fr<FT, RT, NT, LDA>(x2, wsw, w2lane, act_in);
     }
     PPO_STAMP(3);
-    if constexpr (PREF && (!PPO_V_PLATE || EARLY)) pref_data(it + gridDim.x);
-    if constexpr (PREF && PPO_V_PLATE && !EARLY) pref_idx(it + gridDim.x);
+    if constexpr (PREF) pref_data(it + gridDim.x);
     float rs2[RT];
     if constexpr (LN) {
       float mu2[RT];
@@ -1272,9 +1010,7 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
     for (int ht = 0; ht < NHT; ++ht)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) hp[ht][rt] = f4{0.f, 0.f, 0.f, 0.f};
-    // every wave is done reading h1 from ACT: LN2's exchange barrier (ln_rows) already follows every
-    // wave's layer-2 GEMM; tanh trunks and one-wave rows (WF = 1) have no exchange, so they wait here
-    if constexpr (!PPO_V_BAR || !LN || WF == 1) lds_barrier();
+    lds_barrier();  // every wave is done reading h1 from ACT (the h2 rows are written over it below)
     if constexpr (BX) {  // GG shares the activation region: padding heads must read exactly 0
       for (int i = tid; i < R * LDG; i += 256) GG[i] = 0.f;
     }
@@ -1286,12 +1022,11 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
       for (int rt = 0; rt < RT; ++rt) pv[rt] = 0.f;
 #pragma unroll
       for (int ft = 0; ft < FT; ++ft) {
-        const f4 w = (NHT == 1 && PPO_V_HWB) ? hwb[ft] : pld4(pb, K.cW3 + fbase + 4 * g, 16 * ft);
+        const f4 w = pld4(pb, K.cW3 + fbase + 4 * g, 16 * ft);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-          // no LDS copy of the critic's h2: its head backward and dW3 column sums read registers
           const f4 h2 = h2_of(ft, rt);
-          if constexpr (!PPO_V_CH2) lds_st4(ACT + (rbase + 16 * rt + j) * LDA + fbase + 16 * ft + 4 * g, h2);
+          lds_st4(ACT + (rbase + 16 * rt + j) * LDA + fbase + 16 * ft + 4 * g, h2);
 #pragma unroll
           for (int r = 0; r < 4; ++r) pv[rt] = fmaf(w[r], h2[r], pv[rt]);
         }
@@ -1333,26 +1068,20 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
     lds_barrier();
     PPO_STAMP(5);
     float* ITM = SCR;  // R x A x ITS (head partials are consumed)
-    // the critic and the one-row-per-8-lanes Beta loss read each pre-activation straight from the WF
-    // partial sums (same order, bitwise the materialised PRE): no PRE pass and no barrier; the other
-    // losses reuse SCR as item scratch, so they need PRE first
+    // head pre-activations PRE = the WF partial sums (fixed order) + bias, materialised before the loss:
+    // the losses reuse SCR as item scratch
     auto psum = [&](int row, int h) {
       float s = 0.f;
 #pragma unroll
       for (int w = 0; w < WF; ++w) s += SCR[(w * NHP + h) * R + row];
       return s + SHB[h];
     };
-    auto pre = [&](int row, int h) {
-      if constexpr (PPO_V_PRE) return psum(row, h);
-      else return PRE[row * LDG + h];
-    };
-    if (!PPO_V_PRE || !(trunk == 0 || (LN && R == 32 && A <= 8))) {
-      for (int idx = tid; idx < R * nh; idx += 256) {
-        const int row = idx / nh, h = idx - row * nh;
-        PRE[row * LDG + h] = psum(row, h);
-      }
-      lds_barrier();
+    auto pre = [&](int row, int h) { return PRE[row * LDG + h]; };
+    for (int idx = tid; idx < R * nh; idx += 256) {
+      const int row = idx / nh, h = idx - row * nh;
+      PRE[row * LDG + h] = psum(row, h);
     }
+    lds_barrier();
     PPO_STAMP(6);
     // ---------------- loss and its gradient wrt the head pre-activations ----------------
     upd_loss<LN, R, ITS, LDG>(a, trunk, tid, m0, c, adv_mean, adv_std, pre, PRE, GG, ROWS, ACTN, ITM, lst);
@@ -1381,7 +1110,7 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
       for (int rt = 0; rt < RT; ++rt) gr[rt] = lds_f(GG + (rbase + 16 * rt + j) * LDG);
 #pragma unroll
       for (int ft = 0; ft < FT; ++ft) {
-        const f4 w = (NHT == 1 && PPO_V_HWB) ? hwb[ft] : pld4(pb, K.cW3 + fbase + 4 * g, 16 * ft);
+        const f4 w = pld4(pb, K.cW3 + fbase + 4 * g, 16 * ft);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -1394,13 +1123,9 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
 #pragma unroll
       for (int ft = 0; ft < FT; ++ft) {
         f4 wT;
-        if constexpr (NHT == 1 && PPO_V_HWB) {
-          wT = hwb[ft];
-        } else {
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            wT[r] = hrow_b[ht][r] >= 0 ? bld1(pb, hrow_b[ht][r] + fbase + j, 16 * ft) : 0.0f;
-        }
+        for (int r = 0; r < 4; ++r)
+          wT[r] = hrow_b[ht][r] >= 0 ? bld1(pb, hrow_b[ht][r] + fbase + j, 16 * ft) : 0.0f;
         f4 gvv[RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) gvv[rt] = lds_f4(GG + (rbase + 16 * rt + j) * LDG + 16 * ht + 4 * g);
@@ -1466,10 +1191,8 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
     }
     // x2 = dz2
     if (!PPO_DIAG_SKIP(12)) col_sums<FT, RT>([&](int ft, int rt, int r) { return x2[ft][rt][r]; }, acc + sg.b2, fbase, j, g);
-    if (!PPO_DIAG_SKIP(5) && !(DEFER && BX)) store_tile_rows<FT, RT>(a.DZ2[trunk], H, x2, m0, a.M, rbase, fbase, j, g, PPO_DIAG_SKIP(14));
-    // the head backward's readers of h2 / GG (ACT) are done: LN2-backward's exchange barrier (rows_total2)
-    // follows every wave's head backward; without it (tanh, WF = 1) wait here
-    if constexpr (!PPO_V_BAR || !LN || WF == 1) lds_barrier();
+    if (!PPO_DIAG_SKIP(5)) store_tile_rows<FT, RT>(a.DZ2[trunk], H, x2, m0, a.M, rbase, fbase, j, g, PPO_DIAG_SKIP(14));
+    lds_barrier();  // the head backward's readers of h2 / GG (ACT) are done: dz2 is written over them
     if constexpr (BX) lds_store_pieces<FT, RT, LDB, H / 2>(ACT, x2, rbase, fbase, j, g);
     else lds_store_tile<FT, RT, LDA>(ACT, x2, rbase, fbase, j, g);
     lds_barrier();
@@ -1477,17 +1200,12 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
 
     // ---------------- dh1 = W2^T dz2 ----------------
     zero<FT, RT>(dh);
-    if constexpr (BX && DEFER) {
-      mm_bx<FT, RT, NT, LDB>(dh, wbx, w2tblane, actb_in, PPO_DIAG_SKIP(13), [&]() {
-        if (!PPO_DIAG_SKIP(5)) store_rows_from_pieces<FT, RT, LDB, H / 2>(a.DZ2[trunk], H, ACT, m0, a.M, rbase, fbase, j, g);
-      });
-    } else if constexpr (BX) {
+    if constexpr (BX) {
       mm_bx<FT, RT, NT, LDB>(dh, wbx, w2tblane, actb_in, PPO_DIAG_SKIP(13));
     } else {
       mm_fr<FT, RT, NT, LDA>(dh, wsw, w2tlane, act_in);
     }
     PPO_STAMP(10);
-    if constexpr (PREF && PPO_V_PLATE && !EARLY) pref_data(it + gridDim.x);
     // ---------------- recompute layer 1, layer-1 backward ----------------
     init_bias<FT, RT>(z, pb, T.b1 + fbase + 4 * g);
     mm_fr<FT, RT, NTO, LDX, KL1>(z, wsw, w1lane, xn_in);
@@ -1514,7 +1232,6 @@ PPO_DEV void upd16_body(const UpdArgs& a) {
           }
       }
       rows_total2<WF, RT, R>(s1, s2, RED2, RED3, wf, rbase, j, g);
-      if constexpr (EARLY) commit(it + gridDim.x);  // the next tile's rows (see EARLY)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) { s1[rt] *= (1.0f / H); s2[rt] *= (1.0f / H); }
       if (!PPO_DIAG_SKIP(12)) col_sums<FT, RT>([&](int ft, int rt, int r) { return dh[ft][rt][r]; }, acc + sg.be1, fbase, j, g);
