@@ -58,8 +58,13 @@ typedef struct ppo_update_stats {
   int minibatches;
 } ppo_update_stats;
 
-/* sample types for ppo_get_action_and_value (ac:225-238) */
-enum { PPO_SAMPLE = 0, PPO_MEAN = 1, PPO_GIVEN = 2 };
+/* sample types for ppo_get_action_and_value (ac:225-238). PPO_ROACH (LayerNorm-Beta agent only) is
+ * Beta::roach_deterministic (rl_utils.h:112-131), per action dimension on [0, 1] before unscaling:
+ *   alpha > 1, beta > 1: the mode (alpha - 1) / (alpha + beta - 2);  alpha <= 1 < beta: 0;
+ *   beta <= 1 < alpha: 1;  both <= 1: the mean alpha / (alpha + beta).
+ * Log-prob and entropy are those of that action. The tanh-Normal agent refuses it with the
+ * reference's "Unsupported sample type used. Sample type: 3". */
+enum { PPO_SAMPLE = 0, PPO_MEAN = 1, PPO_GIVEN = 2, PPO_ROACH = 3 };
 
 /* storage buffers, all [T, E, *] row-major fp32 (ppo:357-364) */
 enum { PPO_BUF_OBS = 0, PPO_BUF_ACTIONS, PPO_BUF_LOGPROBS, PPO_BUF_REWARDS, PPO_BUF_DONES, PPO_BUF_VALUES,

@@ -53,6 +53,46 @@ int ppo_rollout_synth(struct ppo_ctx* ctx, psyn_t* env, float* next_obs_dev, flo
 enum { PPO_ROLLOUT_AUTO = 0, PPO_ROLLOUT_PER_STEP = 1 };
 int ppo_set_rollout_mode(struct ppo_ctx* ctx, int mode);
 
+/* Policy evaluation on the device env: "what return does this policy get"
+ * (ac_ppo_continuous_action.cpp:965-1001 with num_eval_envs = 1; ppo_continuous_action.cpp:589-626
+ * with num_eval_envs = E).
+ *
+ * psyn_reset(env, eval_seed), then the envs [0, num_eval_envs) each run their own trajectory: act
+ * (Beta mean / roach / sample; Normal mean / sample), clip to the env's action space, SeqVectorEnv
+ * step with next-step autoreset, and the env's wrapper chain if it has one. Every finished episode is
+ * one event (step, env, raw return, length) from the env's RecordEpisodeStatistics state. Returned
+ * are the events ordered by (step, env), up to and including every event of the first step at which
+ * their count reaches num_eval_runs (the reference's while (size < num_eval_runs) around a loop over
+ * all infos of a step): *n_out may exceed num_eval_runs by up to num_eval_envs - 1, and
+ * *env_steps_out is that step + 1. PPO_SAMPLE draws with the key (seed, rank, env, step0 + k) at
+ * evaluation step k, i.e. ppo_get_action_and_value(env_base = 0, step_id = step0 + k).
+ *
+ * The work runs on the context stream in chunks of chunk_steps env steps (0: 4096), one host
+ * synchronisation per chunk; the chunk size changes no returned bit. For the AC agent (LayerNorm-Beta,
+ * hidden 256, obs_dim <= 32, act_dim <= 8) on an env without wrappers a chunk is one persistent launch
+ * (k_eval: actor weights resident in registers, the env step fused in); otherwise, and with mode = 1,
+ * it is chunk_steps x {act launch, psyn_step, event recorder}. Both give bitwise the same result.
+ * ppo_eval_info reports the path the last call took ("eval=k_eval" | "eval=per_step" | "eval=none").
+ *
+ * Refused (-1, ppo_last_error) before any launch: NULL arguments, num_eval_runs <= 0, num_eval_envs
+ * outside [1, E], cap < num_eval_runs + num_eval_envs - 1, PPO_GIVEN, PPO_ROACH on a tanh-Normal
+ * agent, env obs / act dims that differ from the agent's. The call does not touch the rollout storage,
+ * the iteration counter or the parameters; it leaves the env mid-episode (and its finished-episode
+ * sums of psyn_episode_stats include the evaluation's episodes). */
+typedef struct ppo_eval_config {
+  int  sample_type;     /* PPO_SAMPLE | PPO_MEAN | PPO_ROACH */
+  int  eval_seed;
+  int  num_eval_envs;   /* 1: ac:965-1001 (env 0 only); E: ppo:589-626 (all envs) */
+  int  num_eval_runs;
+  long step0;           /* Philox step id of evaluation step 0 (PPO_SAMPLE only) */
+  int  chunk_steps;     /* 0 = default; env steps per launch / per read-out */
+  int  mode;            /* 0 auto, 1 force the per-step path (tests, A/B) */
+} ppo_eval_config;
+
+int ppo_evaluate_synth(struct ppo_ctx* ctx, psyn_t* env, const ppo_eval_config* cfg,
+                       float* returns_host, int* lengths_host, int cap, int* n_out, long* env_steps_out);
+int ppo_eval_info(const struct ppo_ctx* ctx, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -519,23 +519,41 @@ int main(int argc, const char** argv) {
       std::cout << "[ CPUFloatType{" << O << "} ]\n" << std::endl;
     }
     // rank 0 evaluation with the Beta mean action on env 0 (ac:965-1001)
-    if (rank == 0 && !device_env) {
+    if (rank == 0) {
       std::vector<float> episodic_returns;
-      const float* o = envs[0]->reset(config.eval_seed);
-      std::copy(o, o + O, h_obs);
-      long guard = 0;
-      while (episodic_returns.size() < config.num_eval_runs && guard++ < 100000000L) {
-        HIPCHECK(hipMemcpy(d_obs, h_obs, sizeof(float) * O, hipMemcpyHostToDevice));
-        check(ppo_get_action_and_value(agent, 1, d_obs, PPO_MEAN, nullptr, 0, 0, d_act, nullptr, nullptr, nullptr, s),
-              "ppo_get_action_and_value");
-        HIPCHECK(hipStreamSynchronize(s));
-        HIPCHECK(hipMemcpy(h_act, d_act, sizeof(float) * A, hipMemcpyDeviceToHost));
-        gymcpp::VecStep r = envs[0]->step(h_act);
-        std::copy(r.obs, r.obs + O, h_obs);
-        if ((*r.infos)[0].has_value()) {
-          std::cout << "Evaluation result: episode=" << episodic_returns.size() << " episodic_return=" << std::fixed
-                    << std::setprecision(2) << (*r.infos)[0]->r << " \n";
-          episodic_returns.push_back((*r.infos)[0]->r);
+      const auto report = [&](float ret) {
+        std::cout << "Evaluation result: episode=" << episodic_returns.size() << " episodic_return=" << std::fixed
+                  << std::setprecision(2) << ret << " \n";
+        episodic_returns.push_back(ret);
+      };
+      if (device_env) {
+        // the same loop on the device env, inside the library (persistent launches, no host step loop)
+        ppo_eval_config ec{};
+        ec.sample_type = PPO_MEAN;
+        ec.eval_seed = config.eval_seed;
+        ec.num_eval_envs = 1;
+        ec.num_eval_runs = (int)config.num_eval_runs;
+        std::vector<float> rets((size_t)std::max(1, ec.num_eval_runs));
+        std::vector<int> lens(rets.size());
+        int n_eval = 0;
+        long eval_steps = 0;
+        if (ec.num_eval_runs > 0)
+          check(ppo_evaluate_synth(agent, denv, &ec, rets.data(), lens.data(), (int)rets.size(), &n_eval, &eval_steps),
+                "ppo_evaluate_synth");
+        for (int i = 0; i < n_eval; ++i) report(rets[i]);
+      } else {
+        const float* o = envs[0]->reset(config.eval_seed);
+        std::copy(o, o + O, h_obs);
+        long guard = 0;
+        while (episodic_returns.size() < config.num_eval_runs && guard++ < 100000000L) {
+          HIPCHECK(hipMemcpy(d_obs, h_obs, sizeof(float) * O, hipMemcpyHostToDevice));
+          check(ppo_get_action_and_value(agent, 1, d_obs, PPO_MEAN, nullptr, 0, 0, d_act, nullptr, nullptr, nullptr, s),
+                "ppo_get_action_and_value");
+          HIPCHECK(hipStreamSynchronize(s));
+          HIPCHECK(hipMemcpy(h_act, d_act, sizeof(float) * A, hipMemcpyDeviceToHost));
+          gymcpp::VecStep r = envs[0]->step(h_act);
+          std::copy(r.obs, r.obs + O, h_obs);
+          if ((*r.infos)[0].has_value()) report((*r.infos)[0]->r);
         }
       }
       for (size_t i = 0; i < episodic_returns.size(); ++i) logger.add_scalar("eval/episodic_return", (long)i, episodic_returns[i]);

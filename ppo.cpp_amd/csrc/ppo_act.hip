@@ -265,6 +265,8 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
         sv = fminf(fmaxf(sv, 1e-7f), 1.0f + 1e-7f);
       } else if (a.mode == PPO_MEAN) {
         sv = al / (al + be);
+      } else if (a.mode == PPO_ROACH) {
+        sv = beta_roach01(al, be);
       } else {
         sv = beta_sample01(ia[1], ib[1]);
       }

@@ -217,6 +217,7 @@ struct ppo_ctx {
   hipEvent_t sched_ev[2] = {};          // the H2D copy out of sched_host[i] has completed
   int sched_flip = 0;
   float* beta_store = nullptr;          // persistent AC rollout: (alpha, beta, sample) per (t, env, action)
+  int eval_path = 0;                    // last ppo_evaluate_synth: 0 none yet, 1 k_eval, 2 per-step launches
   // profiling
   unsigned prof_mask = 0;
   std::mutex prof_mu;
@@ -807,7 +808,8 @@ extern "C" int ppo_get_action_and_value(ppo_t* c, int n, const float* x, int sam
   if (!c || !x) return fail("ppo_get_action_and_value: null argument");
   if (n <= 0) return 0;
   if (sample_type == PPO_GIVEN && !action_in) return fail("ppo_get_action_and_value: GIVEN needs action_in");
-  if (sample_type < 0 || sample_type > 2) return fail("Unsupported sample type used. Sample type: " + std::to_string(sample_type));
+  if (sample_type < 0 || sample_type > PPO_ROACH || (sample_type == PPO_ROACH && c->K.kind != PPO_NET_LN_BETA))
+    return fail("Unsupported sample type used. Sample type: " + std::to_string(sample_type));
   ActArgs a = base_act(c);
   a.n = n;
   a.x = x;
@@ -1773,6 +1775,107 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
   }
   if (int rc = flush_values(c, c->stream)) return rc;  // the rollout's values, as the persistent path leaves them
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// Policy evaluation on the device env (ac:965-1001 with num_eval_envs = 1; ppo:589-626 with all envs).
+// Chunks of env steps run on the context stream, either as one persistent launch each (k_eval) or as
+// chunk x {act, psyn_step, k_eval_record}; after each chunk one read-out of the event buffer (its
+// counter in the first record) decides whether another chunk is needed. Both paths produce the same
+// events bit for bit, and the kept list depends on the events only (eval_select), not on the chunks.
+extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* cfg, float* returns_host,
+                                  int* lengths_host, int cap, int* n_out, long* env_steps_out) {
+  if (!c || !env || !cfg || !returns_host || !lengths_host || !n_out || !env_steps_out)
+    return fail("ppo_evaluate_synth: null argument");
+  const int E = env->a.E, O = env->a.O, A = env->a.A, nE = cfg->num_eval_envs, runs = cfg->num_eval_runs;
+  if (runs <= 0) return fail("ppo_evaluate_synth: num_eval_runs must be positive");
+  if (nE < 1 || nE > E) return fail("ppo_evaluate_synth: num_eval_envs must be in [1, " + std::to_string(E) + "]");
+  if ((long)cap < (long)runs + nE - 1)
+    return fail("ppo_evaluate_synth: cap must be at least num_eval_runs + num_eval_envs - 1 = " + std::to_string((long)runs + nE - 1));
+  if (cfg->sample_type == PPO_GIVEN) return fail("ppo_evaluate_synth: PPO_GIVEN is not an evaluation sample type");
+  if (cfg->sample_type < 0 || cfg->sample_type > PPO_ROACH || (cfg->sample_type == PPO_ROACH && c->K.kind != PPO_NET_LN_BETA))
+    return fail("Unsupported sample type used. Sample type: " + std::to_string(cfg->sample_type));
+  if (O != c->K.O || A != c->K.A) return fail("ppo_evaluate_synth: env shape mismatch");
+  if (cfg->chunk_steps < 0 || (cfg->mode != 0 && cfg->mode != 1)) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
+  const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : 4096;
+  const bool persistent = cfg->mode == 0 && eval_supported(c->K) == 0 && !env->a.w.on;
+  // the synthetic env truncates after 1000 steps and resets on the next one: an env finishes at most
+  // one episode per 1001 steps, which bounds the events of a chunk (an overflow is still detected)
+  const long devcap = (long)nE * (chunk / 1001 + 2);
+  hipStream_t s = c->stream;
+  struct Scratch {
+    char* p = nullptr;
+    ~Scratch() { if (p) (void)hipFree(p); }
+  } scratch;
+  const size_t nfl = (size_t)E * O + 2 * (size_t)E + (size_t)nE * A;
+  const size_t ev_off = (nfl * sizeof(float) + 15) / 16 * 16;
+  const size_t ev_bytes = (size_t)(devcap + 1) * sizeof(EvalEvent);  // record 0 holds the counter
+  HIP_TRY(hipMalloc((void**)&scratch.p, ev_off + ev_bytes));
+  float* d_obs = reinterpret_cast<float*>(scratch.p);
+  float* d_done = d_obs + (size_t)E * O;
+  float* d_rew = d_done + E;
+  float* d_act = d_rew + E;
+  EvalEvent* d_ev = reinterpret_cast<EvalEvent*>(scratch.p + ev_off);
+  unsigned* d_count = reinterpret_cast<unsigned*>(d_ev);
+  const float lo = env->act_lo, hi = env->act_hi;
+  launch_synth_reset(env->a, cfg->eval_seed, d_obs, d_done, s);
+  std::vector<EvalEvent> all, host((size_t)devcap + 1);
+  long long k = 0, stop = 0;
+  size_t keep = 0;
+  while (keep == 0) {
+    HIP_TRY(hipMemsetAsync(d_ev, 0, sizeof(EvalEvent), s));
+    if (persistent) {
+      EvalArgs a;
+      memset(&a, 0, sizeof(a));
+      a.P = c->P;
+      a.K = c->K;
+      a.WSW = c->WSW[1];
+      a.nE = nE;
+      a.T = chunk;
+      a.step0 = cfg->step0 + (long)k;
+      a.k0 = k;
+      a.seed = c->cfg.seed;
+      a.rank = c->rank;
+      a.mode = cfg->sample_type;
+      a.obs = d_obs;
+      a.env = env->a;
+      a.lo = lo;
+      a.hi = hi;
+      a.ev = d_ev + 1;
+      a.count = d_count;
+      a.cap = (int)devcap;
+      if (launch_eval(a, s) != 0) return fail("ppo_evaluate_synth: evaluation kernel launch failed");
+    } else {
+      for (int t = 0; t < chunk; ++t) {
+        if (int rc = ppo_get_action_and_value(c, nE, d_obs, cfg->sample_type, nullptr, 0, cfg->step0 + (long)(k + t), d_act,
+                                              nullptr, nullptr, nullptr, s))
+          return rc;
+        launch_synth_step(env->a, 0, nE, d_act, lo, hi, d_obs, d_rew, d_done, s);
+        launch_eval_record(env->a, d_done, nE, k + t, d_ev + 1, d_count, (int)devcap, s);
+      }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host.data(), d_ev, ev_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const unsigned got = *reinterpret_cast<const unsigned*>(host.data());
+    if ((long)got > devcap) return fail("ppo_evaluate_synth: event buffer overflow");
+    all.insert(all.end(), host.begin() + 1, host.begin() + 1 + got);
+    k += chunk;
+    keep = eval_select(all, runs, &stop);
+  }
+  for (size_t i = 0; i < keep; ++i) {
+    returns_host[i] = all[i].ret;
+    lengths_host[i] = all[i].len;
+  }
+  *n_out = (int)keep;
+  *env_steps_out = (long)stop + 1;
+  c->eval_path = persistent ? 1 : 2;
+  return 0;
+}
+
+extern "C" int ppo_eval_info(const ppo_t* c, char* buf, int len) {
+  if (!c || !buf || len <= 0) return fail("ppo_eval_info: null argument");
+  snprintf(buf, (size_t)len, "eval=%s", c->eval_path == 1 ? "k_eval" : c->eval_path == 2 ? "per_step" : "none");
   return 0;
 }
 

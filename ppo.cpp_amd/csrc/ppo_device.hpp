@@ -123,6 +123,16 @@ PPO_DEV float beta_sample01(float ga, float gb) {
   return fminf(fmaxf(ga / (ga + gb), 1.17549435e-38f), 0.99999994f);
 }
 
+// Beta::roach_deterministic (rl_utils.h:112-131), PPO_ROACH: the mode where the density has one,
+// the boundary the density piles up at when one concentration is <= 1, the mean when both are.
+// The four cases are exhaustive.
+PPO_DEV float beta_roach01(float al, float be) {
+  if (al > 1.0f && be > 1.0f) return (al - 1.0f) / (al + be - 2.0f);
+  if (al <= 1.0f && be > 1.0f) return 0.0f;
+  if (al > 1.0f && be <= 1.0f) return 1.0f;
+  return al / (al + be);
+}
+
 // Feistel permutation of [0,B) keyed by (seed, rank, epoch counter); replaces torch::randperm
 // (ppo:490, ac:804). Mirrors orc_perm_index.
 struct PermKey {

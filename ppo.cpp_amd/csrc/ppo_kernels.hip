@@ -105,6 +105,8 @@ __global__ __launch_bounds__(64) void k_act(ActArgs a) {
           s = fminf(fmaxf(s, 1e-7f), 1.0f + 1e-7f);
         } else if (a.mode == PPO_MEAN) {
           s = al / (al + be);
+        } else if (a.mode == PPO_ROACH) {
+          s = beta_roach01(al, be);
         } else {
           const float ga = gamma_mt(al, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 0) * 64u);
           const float gb = gamma_mt(be, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 1) * 64u);
@@ -360,6 +362,8 @@ __global__ __launch_bounds__(256) void k_act2(ActArgs a) {
         sv = fminf(fmaxf(sv, 1e-7f), 1.0f + 1e-7f);
       } else if (a.mode == PPO_MEAN) {
         sv = al / (al + be);
+      } else if (a.mode == PPO_ROACH) {
+        sv = beta_roach01(al, be);
       } else {
         const float ga = gamma_mt(al, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 0) * 64u);
         const float gb = gamma_mt(be, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 1) * 64u);

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "ppo_device.hpp"
+#include "ppo_eval_events.hpp"
 #include "ppo_packed.hpp"
 
 #include "../../include/ppo_hip.h"
@@ -299,6 +300,30 @@ struct ValuesArgs {
   long n;
   const float* WBX;     // non-null: the critic's W2 pieces (bx_index): layer 2 as split-bf16 products (k_vbx)
 };
+// Persistent policy evaluation on the device env (ppo_eval.hip, k_eval): one chunk of T env steps of
+// the envs [0, nE) in one launch, the actor's weights resident in registers; finished episodes are
+// appended to ev through the counter (entries past cap are dropped, the counter still counts them).
+struct EvalArgs {
+  const float* P;
+  PackedLayout K;
+  const float* WSW;     // actor trunk's swizzled W1 | W2 | W2^T
+  int nE, T;
+  long step0;           // Philox step id of the chunk's first step (PPO_SAMPLE)
+  long long k0;         // evaluation step index of the chunk's first step
+  uint64_t seed;
+  int rank;
+  int mode;             // PPO_SAMPLE | PPO_MEAN | PPO_ROACH
+  float* obs;           // [nE][O] in: the obs of the chunk's first step; out: the obs after its last
+  SynthArgs env;
+  float lo, hi;         // the env's action space (clip_actions)
+  EvalEvent* ev;
+  unsigned* count;
+  int cap;
+};
+int eval_supported(const PackedLayout& K);
+int launch_eval(const EvalArgs& a, hipStream_t s);  // -1 when the shape / env is not covered
+void launch_eval_record(const SynthArgs& env, const float* done, int nE, long long step, EvalEvent* ev,
+                        unsigned* count, int cap, hipStream_t s);
 int launch_vbx(const ValuesArgs& a, hipStream_t s);  // ppo_update.hip; -1 when the shape is not covered
 int rollout_supported(const PackedLayout& K);
 int launch_rollout(const RolloutArgs& a, hipStream_t s);

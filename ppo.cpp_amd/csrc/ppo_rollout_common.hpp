@@ -1,0 +1,201 @@
+// ppo_rollout_common.hpp — building blocks of the persistent kernels of the 256-wide LayerNorm-Beta
+// agent: k_rollout / k_values (ppo_rollout.hip) and k_eval (ppo_eval.hip). LDS geometry, the per-env
+// scalar slots, the staged small parameters, the register-resident weight slices and one trunk
+// forward for the rows in XS. Kernels that use them in the same order produce bitwise identical
+// results (and bitwise k_act3's, whose blocks of ppo_act_common.hpp they are built from).
+//
+// A translation unit of the diagnostic stamps build defines ROLL_STAMP / RDBG / kRdbgEnv before it
+// includes this file; without them the hooks compile to nothing.
+#pragma once
+
+#include "ppo_act_common.hpp"
+
+#include <type_traits>
+
+#ifndef ROLL_STAMP
+#define ROLL_STAMP(t, k) do {} while (0)
+#endif
+
+namespace {
+
+using namespace act;
+
+constexpr int kRows = 16;  // envs (rows) per workgroup
+
+template <int NTO, int NHT, int ROWS = kRows>
+struct RollGeo {
+  static constexpr int kRows = ROWS;  // rows per pass (16: the rollout's env block; 32: k_values)
+  static constexpr int H = 256, OP = NTO * 16, NHP = 16 * NHT;
+  static constexpr int LDX = ((OP + 63) / 64) * 64 + 4;
+  static constexpr int LDH = H + 4;
+  static constexpr int LDP = NHP + 4;
+  static constexpr int LDQ = OP + 1;                           // env state / obs rows (O <= OP)
+  static constexpr int NSP = 6 * H + NHP * H;
+  static constexpr int oXS = 0;
+  static constexpr int oHB = oXS + kRows * LDX;
+  static constexpr int oSP = oHB + kRows * LDH;
+  static constexpr int oHBIAS = oSP + NSP;
+  static constexpr int oRED = oHBIAS + NHP;
+  static constexpr int oHP = oRED + 2 * kActWaves * kRows;
+  static constexpr int oPRE = oHP + kActWaves * NHP * kRows;
+  static constexpr int oXO = oPRE + kRows * LDP;               // agent input obs of the current step
+  static constexpr int oQ = oXO + kRows * LDQ;                 // env state q
+  static constexpr int oNRM = oQ + kRows * LDQ;                // obs mean | std (OP each)
+  static constexpr int oACT = oNRM + 2 * OP;                   // actions [16][24]
+  static constexpr int oENV = oACT + kRows * 24;               // per-env scalars, 16 x 16
+  static constexpr int total = oENV + 16 * kRows;
+  // distribution scratch in the XS / HB region (dead after layer 2), as in k_act3
+  static constexpr int oITM = 0;
+  static constexpr int oLP = oITM + kRows * 24 * 2 * 4;
+  static_assert(oLP + kRows * 24 * 2 <= oSP, "distribution scratch must fit in the XS/HB region");
+  // staged param vectors inside SP (as ActGeo)
+  static constexpr int sB1 = 0, sG1 = H, sBE1 = 2 * H, sB2 = 3 * H, sG2 = 4 * H, sBE2 = 5 * H, sW3 = 6 * H;
+};
+
+// per-env scalar slots in the oENV region
+// (the wrapper chain's per-env scalars: obs count, return accumulator, reward mean / var / count)
+enum { EV_DONE = 0, EV_AR, EV_T, EV_RSEED, EV_RCOUNT, EV_EPR, EV_EPL, EV_FR, EV_FL, EV_FC,
+       EV_WOC, EV_WRA, EV_WRM, EV_WRV, EV_WRC, EV_NSLOT };
+
+// staged small parameters of one trunk into LDS (biases, LayerNorm affine, head rows, head biases)
+template <int NHP>
+PPO_DEV void stage_params(const PackedLayout& K, const TrunkDev& T, PBuf pb, int trunk, float* SP, float* HBIAS,
+                          int tid) {
+  constexpr int H = 256, NSP4 = (6 * H + NHP * H) / 4;
+  for (int q = tid; q < NSP4; q += kActThreads) {
+    const int fl = 4 * q, vec = fl / H, off = fl - vec * H;
+    int src = -1;
+    if (vec < 6) {
+      const int base = vec == 0 ? T.b1 : vec == 1 ? T.g1 : vec == 2 ? T.be1 : vec == 3 ? T.b2 : vec == 4 ? T.g2 : T.be2;
+      src = base >= 0 ? base + off : -1;
+    } else {
+      const int hr = act_head_row(K, trunk, vec - 6);
+      src = hr >= 0 ? hr + off : -1;
+    }
+    *reinterpret_cast<f4*>(SP + fl) = pld4(pb, src >= 0 ? src : K.size, 0);
+  }
+  if (tid < NHP) {
+    const int hbo = act_head_bias(K, trunk, tid);
+    HBIAS[tid] = bld1f(pb, hbo >= 0 ? hbo : K.size);
+  }
+}
+
+// One trunk forward for the 16 rows whose (normalised, zero-padded) inputs are in XS: layer 1,
+// LayerNorm + ReLU, layer 2, LayerNorm + ReLU, heads; leaves the head pre-activations (+ bias) in
+// PRE [16][LDP]. Weights: w1 / w2 register slices of this wave. Same operations, same order as
+// k_act3 (LN_BETA, RT = 1).
+// PRE_PASS false: stop once the per-wave head partials are in HP (after the barrier); the caller
+// adds them itself (the same adds in the same order: bitwise the PRE values).
+template <int NTO, int NHT, int RT = 1, bool PRE_PASS = true, typename PRE_L2 = int>
+PPO_DEV void trunk_rows(const f4 (&w1)[NTO][2], const f4 (&w2)[16][2], float* lds, int nh, int tid,
+                        PRE_L2 pre_l2 = 0, int stamp_t = -1) {
+  (void)stamp_t;  // ROLL_STAMP step index (stamps build; -1: none)
+  using GE = RollGeo<NTO, NHT, 16 * RT>;
+  constexpr int H = 256, LDX = GE::LDX, LDH = GE::LDH, LDP = GE::LDP, NHP = GE::NHP, R = 16 * RT;
+  float* XS = lds + GE::oXS;
+  float* HB = lds + GE::oHB;
+  float* SP = lds + GE::oSP;
+  float* HBIAS = lds + GE::oHBIAS;
+  float* RED = lds + GE::oRED;
+  float* HP = lds + GE::oHP;
+  float* PRE = lds + GE::oPRE;
+  const int lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+  f4 acc[2][RT];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const f4 b1 = *reinterpret_cast<const f4*>(SP + GE::sB1 + 32 * wave + 16 * u + 4 * g);
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[u][rt] = b1;
+  }
+  const float* xin = XS + j * LDX + 4 * g;
+  act_layer_regs<NTO, RT>(acc, w1, [&](int t, int rt) { return *reinterpret_cast<const f4*>(xin + 16 * rt * LDX + 16 * t); });
+#ifdef RDBG
+  const bool dbg = stamp_t == 0 && RT == 1 && (int)blockIdx.x * 16 + j == kRdbgEnv;
+  auto dump = [&](int base) {
+    if (dbg)
+      for (int u = 0; u < 2; ++u)
+        for (int r = 0; r < 4; ++r) RDBG(0, base + 32 * wave + 16 * u + 4 * g + r, acc[u][0][r]);
+  };
+#else
+  auto dump = [](int) {};
+#endif
+  dump(0);
+  act_activate<PPO_NET_LN_BETA, RT>(acc, SP + GE::sG1, SP + GE::sBE1, RED, wave, j, g);
+  dump(260);
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+      *reinterpret_cast<f4*>(HB + (16 * rt + j) * LDH + 32 * wave + 16 * u + 4 * g) = acc[u][rt];
+  lds_barrier();
+  if (stamp_t >= 0) ROLL_STAMP(stamp_t, 5);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const f4 b2 = *reinterpret_cast<const f4*>(SP + GE::sB2 + 32 * wave + 16 * u + 4 * g);
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[u][rt] = b2;
+  }
+  const float* hin = HB + j * LDH + 4 * g;
+  // independent VALU work placed in the layer-2 block: the scheduler interleaves it with the MFMAs,
+  // whose issue leaves the SIMD's vector pipe mostly free
+  if constexpr (!std::is_same_v<PRE_L2, int>) pre_l2();
+  act_layer_regs<16, RT>(acc, w2, [&](int t, int rt) { return *reinterpret_cast<const f4*>(hin + 16 * rt * LDH + 16 * t); });
+  if (stamp_t >= 0) {
+#ifdef PPO_STAMPS
+    asm volatile("s_nop 0" ::"v"(acc[0][0].x), "v"(acc[1][0].x));  // the layer-2 results exist here
+#endif
+    ROLL_STAMP(stamp_t, 6);
+  }
+  dump(516);
+  act_activate<PPO_NET_LN_BETA, RT>(acc, SP + GE::sG2, SP + GE::sBE2, RED, wave, j, g);
+  dump(776);
+  if (stamp_t >= 0) ROLL_STAMP(stamp_t, 7);
+#pragma unroll
+  for (int ht = 0; ht < NHT; ++ht) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      f4 hp = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const f4 wv = *reinterpret_cast<const f4*>(SP + GE::sW3 + (16 * ht + j) * H + 32 * wave + 16 * u + 4 * g);
+        hp = mfma16(wv.x, acc[u][rt].x, hp);
+        hp = mfma16(wv.y, acc[u][rt].y, hp);
+        hp = mfma16(wv.z, acc[u][rt].z, hp);
+        hp = mfma16(wv.w, acc[u][rt].w, hp);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) HP[(wave * NHP + 16 * ht + 4 * g + r) * R + 16 * rt + j] = hp[r];
+#ifdef RDBG
+      if (dbg && ht == 0)
+        for (int r = 0; r < 4; ++r) RDBG(0, 1032 + wave * 16 + 4 * g + r, hp[r]);
+#endif
+    }
+  }
+  lds_barrier();
+  if constexpr (!PRE_PASS) return;
+  for (int idx = tid; idx < R * nh; idx += kActThreads) {
+    const int r = idx / nh, h = idx - r * nh;
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < kActWaves; ++w) s += HP[(w * NHP + h) * R + r];
+    PRE[r * LDP + h] = s + HBIAS[h];
+  }
+  lds_barrier();
+}
+
+// this wave's register slices of a trunk's W1 (NTO k-blocks) and W2 (16 k-blocks), 2 feature tiles
+template <int NTO>
+PPO_DEV void load_weight_slices(PBuf wsw, int wave, int lane, f4 (&w1)[NTO][2], f4 (&w2)[16][2]) {
+  constexpr int H = 256, OP = NTO * 16;
+  const int l1 = ((2 * wave) * NTO * 64 + lane) * 4;
+  const int l2 = H * OP + ((2 * wave) * 16 * 64 + lane) * 4;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+#pragma unroll
+    for (int t = 0; t < NTO; ++t) w1[t][u] = pld4(wsw, l1, 256 * (NTO * u + t));
+#pragma unroll
+    for (int t = 0; t < 16; ++t) w2[t][u] = pld4(wsw, l2, 256 * (16 * u + t));
+  }
+}
+
+}  // namespace

@@ -36,7 +36,7 @@ LIB_PATH = os.environ.get("PPO_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libpp
 
 PPO_NET_TANH_NORMAL = 0
 PPO_NET_LN_BETA = 1
-PPO_SAMPLE, PPO_MEAN, PPO_GIVEN = 0, 1, 2
+PPO_SAMPLE, PPO_MEAN, PPO_GIVEN, PPO_ROACH = 0, 1, 2, 3
 (BUF_OBS, BUF_ACTIONS, BUF_LOGPROBS, BUF_REWARDS, BUF_DONES, BUF_VALUES, BUF_ADVANTAGES,
  BUF_RETURNS) = range(8)
 MAX_T = 32
@@ -154,6 +154,11 @@ class CarlaRolloutConfig(C.Structure):  # ppo_carla_rollout_config
 CARLA_BUFFERS = ("bev", "meas", "vmeas", "actions", "logp", "rewards", "dones", "values", "adv", "returns",
                  "next_value")
 
+class EvalConfig(C.Structure):  # ppo_eval_config (include/ppo_synth_env.h)
+    _fields_ = [("sample_type", C.c_int), ("eval_seed", C.c_int), ("num_eval_envs", C.c_int),
+                ("num_eval_runs", C.c_int), ("step0", C.c_long), ("chunk_steps", C.c_int), ("mode", C.c_int)]
+
+
 _LIB = None
 
 # (name, restype, argtypes) of every entry point declared in include/ppo_hip.h / ppo_synth_env.h /
@@ -220,6 +225,8 @@ SYMBOLS = [
     ("psyn_episode_stats_begin", _I, [_VP, _VP]),
     ("psyn_episode_stats_end", _I, [_VP, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F)]),
     ("ppo_rollout_synth", _I, [_VP, _VP, _FP, _FP, _FP, _FP]),
+    ("ppo_evaluate_synth", _I, [_VP, _VP, C.POINTER(EvalConfig), _FP, _VP, _I, C.POINTER(_I), C.POINTER(_L)]),
+    ("ppo_eval_info", _I, [_VP, C.c_char_p, _I]),
     ("psyn_set_action_space", _I, [_VP, _F, _F]),
     ("ppo_set_rollout_mode", _I, [_VP, _I]),
     ("psyn_action_space", _I, [_VP, C.POINTER(_F), C.POINTER(_F)]),
@@ -742,6 +749,26 @@ class Agent:
         """The update / dW kernels this context selected (ppo_kernel_info)."""
         buf = C.create_string_buffer(256)
         check(lib().ppo_kernel_info(self.h, buf, 256))
+        return buf.value.decode()
+
+    def evaluate(self, env: "SynthEnv", num_eval_runs, sample_type=PPO_MEAN, eval_seed=2, num_eval_envs=1, step0=0,
+                 chunk_steps=0, per_step=False):
+        """ppo_evaluate_synth: resets env with eval_seed and runs envs [0, num_eval_envs) with this policy
+        until num_eval_runs episodes have finished (all episodes of that step are kept). Returns
+        (episodic returns float32[n], episode lengths int32[n], env steps taken); per_step forces the
+        per-step launches (bitwise the same result)."""
+        cfg = EvalConfig(sample_type, eval_seed, num_eval_envs, num_eval_runs, step0, chunk_steps, 1 if per_step else 0)
+        cap = max(1, num_eval_runs + num_eval_envs - 1)
+        ret, ln = np.zeros(cap, np.float32), np.zeros(cap, np.int32)
+        n, steps = C.c_int(), C.c_long()
+        check(lib().ppo_evaluate_synth(self.h, env.h, C.byref(cfg), ret.ctypes.data, ln.ctypes.data, cap, C.byref(n),
+                                       C.byref(steps)))
+        return ret[:n.value].copy(), ln[:n.value].copy(), steps.value
+
+    def eval_info(self):
+        """The path the last evaluate() took: "eval=k_eval" | "eval=per_step" | "eval=none" (ppo_eval_info)."""
+        buf = C.create_string_buffer(64)
+        check(lib().ppo_eval_info(self.h, buf, 64))
         return buf.value.decode()
 
     def set_rollout_mode(self, per_step: bool):
