@@ -1,8 +1,14 @@
-// ppo_carla_internal.hpp — what ppo_carla_rollout.hip needs from the agent beyond include/ppo_carla.h
-// (defined at the end of ppo_carla.hip). The rollout object computes through ppo_carla_forward /
-// ppo_carla_update and, for its act lanes, carla_forward on a lane's own buffer set; the rest reads the
-// agent's placement and moves the statistics that every ppo_carla_update leaves on the device, so the
-// epoch loop needs no host synchronisation per minibatch.
+// ppo_carla_internal.hpp — the CaRL agent beyond include/ppo_carla.h, for the units of the library:
+//   ppo_carla.hip          the agent: context, layer table, forward, update, I/O, the entry points below
+//   ppo_carla_conv.hip     forward convolution kernels (a Linear layer is a 1x1 one), launch_conv
+//   ppo_carla_tail.hip     k_carla_pack, k_carla_head, k_carla_tail and their launchers
+//   ppo_carla_ln.hip       LayerNorm kernels and launchers, the ppo_carla_debug_ln_* hooks
+//   ppo_carla_grad.hip     input- and weight-gradient kernels and launchers
+//   ppo_carla_rollout.hip  rollout storage, GAE, the epoch loop, act lanes
+// (ppo_carla_units.hpp: what crosses the first five). The rollout object computes through
+// ppo_carla_forward / ppo_carla_update and, for its act lanes, carla_forward on a lane's own buffer set;
+// the rest reads the agent's placement and moves the statistics that every ppo_carla_update leaves on the
+// device, so the epoch loop needs no host synchronisation per minibatch.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -45,6 +51,48 @@ struct CarlaFwdBufs {
   Ln ln[kLnCount];
   bool any_ln = false;
 };
+
+// ---- the MLP part of the network (carla_model.h:238-279), described once ----
+// Its activation buffers by name: a layer names what it reads and writes, so one table serves every buffer
+// set and the gradient buffers. kBufMeas is the caller's measurements (in no set); kBufState is columns
+// 1024.. of enc (state_linear's output beside conv6's); feat is [256 + NV]: features | value measurements.
+enum CarlaBuf { kBufMeas, kBufS1, kBufState, kBufEnc, kBufL1, kBufFeat, kBufV1, kBufV2, kBufVal, kBufP1, kBufP2, kBufCount };
+static inline float* carla_buf(const CarlaFwdBufs& fb, int name) {
+  float* const p[kBufCount] = {nullptr, fb.s1, fb.enc + 1024, fb.enc, fb.l1, fb.feat, fb.v1, fb.v2, fb.val, fb.p1, fb.p2};
+  return p[name];
+}
+// The gradient of each named buffer (allocated by the first update). d[kBufMeas] and d[kBufState] stay
+// null: kBufState's is part of d[kBufEnc]. Rows are as wide as the buffer's, except that d[kBufFeat] has
+// no value-measurement columns.
+struct CarlaGradBufs {
+  float* d[kBufCount] = {};
+};
+static inline float* carla_grad(const CarlaGradBufs& g, int name) { return name == kBufState ? g.d[kBufEnc] + 1024 : g.d[name]; }
+static inline long carla_grad_stride(int name) {
+  return name == kBufEnc || name == kBufState ? 1280 : name == kBufL1 ? 512 : name == kBufVal ? 1 : 256;
+}
+// One Linear layer. CarlaNet (built once by ppo_carla_create2) lists the nine in carla_model.h's forward
+// order; buffer sizes, the per-layer forward, the fused tail's arguments and the backward are loops over it.
+// The backward is the reverse order, and a layer adds to its input's gradient exactly when a layer after it
+// in the forward has stored it (feat, read by both heads); the fused tail runs tail_order, the layers stably
+// sorted by stage. dist_mu / dist_sigma are not listed: k_carla_head / k_carla_head_bwd compute them.
+struct CarlaLayer {
+  int in, out;                 // CarlaBuf
+  long in_stride, out_stride;  // floats per row
+  int IN, OUT;                 // columns read (value_head.0: 256 + NV of feat, policy_head.0: 256) and written
+  long w, b;                   // offsets in the parameter vector
+  int relu;
+  int ln;        // CarlaFwdBufs::kLn* slot of the LayerNorm after it (used when the slot's F != 0), -1: none
+  long g, be;    // that LayerNorm's gamma / beta offsets, -1: none
+  int stage;     // fused tail: dependency stage (0: beside conv6's finish)
+  bool to_value; // fused tail: column 0 also goes to the caller's `value`
+};
+constexpr int kCarlaLayers = 9;
+struct CarlaNet {
+  CarlaLayer layer[kCarlaLayers];
+  int tail_order[kCarlaLayers];
+};
+
 // a zeroed buffer set of `rows` rows for c's shapes on the current device; -2 if an allocation fails
 // (the caller frees what was allocated). The zero fills run on the null stream.
 int carla_fwd_alloc(const ppo_carla_t* c, size_t rows, CarlaFwdBufs* fb);
