@@ -303,7 +303,8 @@ int ppo_carla_forward(ppo_carla_t* c, int n, const uint8_t* bev, const float* me
  * Loss = pg_loss - ent_coef * entropy + vf_coef * v_loss exactly as the MLP agents (clipped
  * surrogate, clipped value loss, minibatch advantage normalisation with Bessel's correction),
  * backward through heads, MLPs and all six convolutions, clip_grad_norm_(max_grad_norm), Adam
- * (betas 0.9 / 0.999, eps = adam_eps, bias-corrected, weight_decay 0), all on the device. */
+ * (eps = adam_eps, bias-corrected; betas 0.9 / 0.999 and weight_decay 0 unless ppo_carla_set_adam
+ * says otherwise), all on the device. */
 typedef struct ppo_carla_train_config {
   float clip_coef;      /* 0.2 */
   float ent_coef;       /* 0.0 */
@@ -331,6 +332,29 @@ int ppo_carla_last_grad(ppo_carla_t* c, float* host, long n);
 /* Adam moments in the same flat order, and the step count */
 int ppo_carla_save_adam(ppo_carla_t* c, float* m_host, float* v_host, long n, long* step);
 int ppo_carla_load_adam(ppo_carla_t* c, const float* m_host, const float* v_host, long n, long step);
+/* The optimizer's betas and weight decay (the reference's Adam(lr).eps(adam_eps).weight_decay(weight_decay)
+ * .betas(beta_1, beta_2), ac_ppo_carla.cpp:246; defaults 0.9, 0.999, 0). They belong to the agent and
+ * persist across ppo_carla_update, ppo_carla_rollout_train and ppo_carla_load_adam. LibTorch's C++
+ * Adam::step after clip_grad_norm_, on every trainable tensor (LayerNorm weights and biases included;
+ * action_space_high / _low are never touched):
+ *   g = G * coef;  g += (float)wd * p            (coupled L2, not AdamW)
+ *   m = m * (float)b1 + g * (float)(1.0 - b1);   v = v * (float)b2 + g * g * (float)(1.0 - b2)
+ *   p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps),  step_size = lr / bc1, bc = 1 - pow(b, step) in double
+ * Options of exactly (0.9, 0.999, 0) launch k_carla_adam, which has them compiled in: such an agent's
+ * bits are those of one that never called ppo_carla_set_adam. Any other options launch k_carla_adam_opt.
+ * Refused before any HIP call: NULL arguments, a beta outside [0, 1), a negative or non-finite weight
+ * decay. Like ppo_carla_load_adam, it must not be called while an update or a lane call of the agent is
+ * inside the library. */
+int ppo_carla_set_adam(ppo_carla_t* c, double beta1, double beta2, double weight_decay);
+int ppo_carla_get_adam(const ppo_carla_t* c, double* beta1, double* beta2, double* weight_decay);
+
+/* test hook: `reps` back-to-back launches of k_carla_adam, then of k_carla_adam_opt with the given options,
+ * over the agent's trainable range, each run timed with HIP events on the agent's stream after three
+ * warm-up launches; microseconds per launch. It steps the agent's parameters and moments with whatever
+ * gradient is there (lr 3e-4, no bias correction) and leaves the step count and options alone: for a
+ * scratch agent only. */
+int ppo_carla_debug_adam_time(ppo_carla_t* c, int reps, double beta1, double beta2, double weight_decay,
+                              float* us_default, float* us_opt);
 
 /* ---- test hooks: the LayerNorm launches of the agent on caller arrays (device pointers) ----------
  * forward: y[r, 0..F) = relu(layer_norm(z[r, 0..F)) * gamma + beta) for n rows of strides in_stride /
@@ -440,6 +464,13 @@ int ppo_carla_rollout_gae(ppo_carla_rollout_t* r, const uint8_t* next_bev, const
 int ppo_carla_rollout_train(ppo_carla_rollout_t* r, const ppo_carla_train_config* tc, float lr,
                             int num_steps_collected, const int32_t* perms_dev, ppo_carla_update_stats* last,
                             float* mean_clipfrac);
+/* losses/discounted_returns (:626-658, :701): *out (host) = the mean of the returns of the last
+ * ppo_carla_rollout_gae over the num_steps_collected * E collected rows, repeated and truncated to
+ * B = T * E as the permutation is, then averaged over the ranks of an attached communicator. One
+ * fixed-order reduction (k_carla_returns_mean, one block) on the agent's stream: two calls give the
+ * same bits, and a one-rank communicator changes none. Synchronises that stream. Refused like
+ * ppo_carla_rollout_train while a lane call is inside the library. */
+int ppo_carla_rollout_returns_mean(ppo_carla_rollout_t* r, int num_steps_collected, float* out);
 /* device pointer of a storage array (PPO_CARLA_BUF_*) */
 int ppo_carla_rollout_buffer(ppo_carla_rollout_t* r, int which, void** dev_ptr);
 /* host copy of the indices the last ppo_carla_rollout_train used: n = update_epochs * T * E */

@@ -60,6 +60,15 @@ int ppo_carla_pth_save_adam2(const ppo_carla_layout2* L, const float* m, const f
                              double eps, const char* path);
 int ppo_carla_pth_load_adam2(const ppo_carla_layout2* L, const char* path, float* m, float* v, long n, long* step,
                              double* lr_out, double* eps_out);
+/* the same with the betas and the weight decay of the archive's options (ppo_carla_set_adam; the
+ * reference's Adam(lr).eps(adam_eps).weight_decay(weight_decay).betas(beta_1, beta_2), :246). The *2 pair
+ * writes (0.9, 0.999) and 0 and drops what it reads; an archive written by save_adam3 with those values
+ * is byte-identical to save_adam2's, and either loader reads either file. Every *_out may be NULL. */
+int ppo_carla_pth_save_adam3(const ppo_carla_layout2* L, const float* m, const float* v, long step, double lr,
+                             double eps, double beta1, double beta2, double weight_decay, const char* path);
+int ppo_carla_pth_load_adam3(const ppo_carla_layout2* L, const char* path, float* m, float* v, long n, long* step,
+                             double* lr_out, double* eps_out, double* beta1_out, double* beta2_out,
+                             double* weight_decay_out);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,9 @@
 // avg_episodic_return=...", "SPS: ..."), TensorBoard scalars, model_latest_%09d.pth /
 // optimizer_latest_%09d.pth with the previous pair removed (:664-683), model_best.pth /
 // optimizer_best.pth on a new windowed best (:456-474), config.json beside them. --load_file
-// <...>/model_latest_%09d.pth resumes at the next iteration with the optimizer and the counters of
-// that folder's config.json (:226-255).
+// <...>/model_latest_%09d.pth resumes at the next iteration with every setting of that folder's config.json,
+// the arguments applied again on top (:90-99), and the optimizer with its archive's betas and weight decay
+// (:226-255).
 //
 // DD-PPO preemption (--use_dd_ppo_preempt 1, :268-282, :343-345, :399-413): rank 0 serves the TCP store,
 // every env has a client; an env stops collecting once more than dd_ppo_preempt_threshold of all envs
@@ -23,8 +24,11 @@
 // total over ranks, each rank connects to ports[num_envs_per_proc * local_rank + i]. The RCCL id
 // travels through --rdzv_file. The agent's update averages advantage statistics and gradients.
 //
-// Flags: the ones this loop reads, with the names and defaults of carla_config.h. The OpenCV
-// visualisation and the reward / rendering options of the Python side are not part of this build.
+// Flags and config: every option of carla_config.h with its name, type and default (apps/carla_config.h: one
+// table for the flags, the JSON sent to the gyms on <port>.conf_lock, config.json and its reader). The
+// reward / rendering / termination options are stored and forwarded, as in the reference's trainer; beta_1,
+// beta_2 and weight_decay reach the device optimizer (ppo_carla_set_adam) and the optimizer archive. Not
+// built: collect_device / train_device cpu, the OpenCV view of --debug 1, roach_ln2, use_positional_encoding.
 #include <hip/hip_runtime.h>
 
 #include <deque>
@@ -38,103 +42,13 @@
 #include "../../include/ppo_pth.h"
 #include "../gymcpp/carla_gym.h"
 #include "../net/zmtp.h"
+#include "carla_config.h"
 #include "json_flat.h"
 #include "tcp_store.h"
 #include "trainer_common.h"
 
 using namespace app;
 namespace fs = std::filesystem;
-
-struct GlobalConfig {
-  int seed = 1;
-  int total_timesteps = 1'000'000;
-  float learning_rate = 3e-4f;
-  int num_envs = 1;
-  int num_steps = 2048;
-  float gamma = 0.99f;
-  float gae_lambda = 0.95f;
-  int num_minibatches = 32;
-  int update_epochs = 10;
-  bool norm_adv = true;
-  float clip_coef = 0.2f;
-  bool clip_vloss = true;
-  float ent_coef = 0.0f;
-  float vf_coef = 0.5f;
-  float max_grad_norm = 0.5f;
-  float adam_eps = 1e-5f;
-  std::string lr_schedule = "linear";
-  bool clip_actions = true;
-  std::vector<int> gpu_ids = {0};
-  std::string rdzv_addr = "localhost";
-  int tcp_store_port = 29500;
-  int use_dd_ppo_preempt = 0;
-  float dd_ppo_min_perc = 0.25f;
-  float dd_ppo_preempt_threshold = 0.6f;
-  std::vector<int> ports = {5555};
-  float beta_min_a_b_value = 1.0f;
-  int obs_num_channels = 15;
-  std::string image_encoder = "roach";
-  bool use_layer_norm = false;
-  bool use_layer_norm_policy_head = true;
-  bool use_positional_encoding = false;
-  int obs_num_measurements = 8;
-  int bev_semantics_width = 192, bev_semantics_height = 192;
-  int num_value_measurements = 3;
-  std::string team_code_folder = "";
-  std::string load_file = "None";
-  std::string logdir = "";
-  std::string exp_name = "";
-  std::string rdzv_file = "";
-  // counters kept in config.json across restarts
-  long global_step = 0;
-  float max_training_score = std::numeric_limits<float>::lowest();
-  long best_iteration = 0;
-  long latest_iteration = 0;
-  // derived (carla_config.h:131-138)
-  int num_devices = 1, batch_size = 0, minibatch_size = 0, num_iterations = 0, num_envs_per_proc = 0;
-  int batch_size_per_device = 0, minibatch_per_device = 0;
-
-  void derive(int world_size) {
-    num_devices = world_size;
-    if (exp_name.empty()) exp_name = "PPO_002_" + std::to_string(seed);
-    batch_size = num_steps * num_envs;
-    minibatch_size = batch_size / std::max(1, num_minibatches);
-    num_iterations = batch_size > 0 ? total_timesteps / batch_size : 0;
-    num_envs_per_proc = num_envs / num_devices;
-    batch_size_per_device = batch_size / num_devices;
-    minibatch_per_device = minibatch_size / num_devices;
-  }
-
-  // the flat object the leaderboard gyms and a later --load_file read (carla_config.h to_json)
-  std::string to_json() const {
-    std::ostringstream o;
-    o << std::setprecision(9) << "{\n";
-    auto num = [&](const char* k, double v) { o << "  \"" << k << "\": " << v << ",\n"; };
-    auto str = [&](const char* k, const std::string& v) { o << "  \"" << k << "\": \"" << v << "\",\n"; };
-    auto lng = [&](const char* k, long v) { o << "  \"" << k << "\": " << v << ",\n"; };
-    auto boo = [&](const char* k, bool v) { o << "  \"" << k << "\": " << (v ? "true" : "false") << ",\n"; };
-    num("seed", seed); lng("total_timesteps", total_timesteps); num("learning_rate", learning_rate);
-    num("num_envs", num_envs); num("num_steps", num_steps); num("gamma", gamma); num("gae_lambda", gae_lambda);
-    num("num_minibatches", num_minibatches); num("update_epochs", update_epochs); boo("norm_adv", norm_adv);
-    num("clip_coef", clip_coef); boo("clip_vloss", clip_vloss); num("ent_coef", ent_coef); num("vf_coef", vf_coef);
-    num("max_grad_norm", max_grad_norm); num("adam_eps", adam_eps); str("lr_schedule", lr_schedule);
-    boo("clip_actions", clip_actions); str("rdzv_addr", rdzv_addr); num("tcp_store_port", tcp_store_port);
-    num("use_dd_ppo_preempt", use_dd_ppo_preempt); num("dd_ppo_min_perc", dd_ppo_min_perc);
-    num("dd_ppo_preempt_threshold", dd_ppo_preempt_threshold); num("beta_min_a_b_value", beta_min_a_b_value);
-    num("obs_num_channels", obs_num_channels); str("image_encoder", image_encoder);
-    boo("use_layer_norm", use_layer_norm); boo("use_layer_norm_policy_head", use_layer_norm_policy_head);
-    boo("use_positional_encoding", use_positional_encoding); num("obs_num_measurements", obs_num_measurements);
-    num("bev_semantics_width", bev_semantics_width); num("bev_semantics_height", bev_semantics_height);
-    num("num_value_measurements", num_value_measurements); str("team_code_folder", team_code_folder);
-    str("logdir", logdir); str("exp_name", exp_name); num("num_devices", num_devices); num("batch_size", batch_size);
-    num("minibatch_size", minibatch_size); num("num_iterations", num_iterations);
-    num("num_envs_per_proc", num_envs_per_proc); num("batch_size_per_device", batch_size_per_device);
-    num("minibatch_per_device", minibatch_per_device); lng("global_step", global_step);
-    num("max_training_score", max_training_score); lng("best_iteration", best_iteration);
-    o << "  \"latest_iteration\": " << latest_iteration << "\n}\n";
-    return o.str();
-  }
-};
 
 static int env_int(const char* a, const char* b, int def) {
   if (const char* v = std::getenv(a)) return std::atoi(v);
@@ -172,13 +86,15 @@ static std::vector<float> init_carla_params(const ppo_carla_layout2& L, int seed
 // save_state (:62-73): model, optimizer and config.json
 static void save_state(ppo_carla_t* agent, const ppo_carla_layout2& L, const fs::path& folder,
                        const std::string& model_file, const std::string& optimizer_file, double lr,
-                       const GlobalConfig& config) {
+                       GlobalConfig& config) {
   std::vector<float> p(L.P), m(L.P), v(L.P);
   long step = 0;
   check(ppo_carla_save_params(agent, p.data(), L.P), "ppo_carla_save_params");
   check(ppo_carla_save_adam(agent, m.data(), v.data(), L.P, &step), "ppo_carla_save_adam");
   check(ppo_carla_pth_save2(&L, p.data(), (folder / model_file).string().c_str()), "torch::save of the model");
-  check(ppo_carla_pth_save_adam2(&L, m.data(), v.data(), step, lr, config.adam_eps,
+  double b1 = 0.0, b2 = 0.0, wd = 0.0;  // the agent's: exactly (0.9, 0.999, 0) unless ppo_carla_set_adam was called
+  check(ppo_carla_get_adam(agent, &b1, &b2, &wd), "ppo_carla_get_adam");
+  check(ppo_carla_pth_save_adam3(&L, m.data(), v.data(), step, lr, config.adam_eps, b1, b2, wd,
                                  (folder / optimizer_file).string().c_str()),
         "torch::save of the optimizer");
   std::ofstream out((folder / "config.json").string());
@@ -193,85 +109,42 @@ int main(int argc, const char** argv) {
   const int local_rank = env_int("LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", rank);
 
   GlobalConfig config;
-  Flags flags;
   std::vector<int> ports_given, gpu_ids_given;
-  flags.add("seed", "Training seed", &config.seed);
-  flags.add("total_timesteps", "Number of environment steps", &config.total_timesteps);
-  flags.add("learning_rate", "Adam learning rate", &config.learning_rate);
-  flags.add("num_envs", "Number of environments to be used (over all ranks).", &config.num_envs);
-  flags.add("num_steps", "Num environment steps per iteration", &config.num_steps);
-  flags.add("gamma", "Discount factor", &config.gamma);
-  flags.add("gae_lambda", "Lambda of generalized advantage estimation", &config.gae_lambda);
-  flags.add("num_minibatches", "Number of training iterations per epoch", &config.num_minibatches);
-  flags.add("update_epochs", "Number of training epochs per iteration", &config.update_epochs);
-  flags.add("norm_adv", "Whether to normalize the advantage", &config.norm_adv);
-  flags.add("clip_coef", "PPO clip coefficient", &config.clip_coef);
-  flags.add("clip_vloss", "Whether to apply clipping to the value loss", &config.clip_vloss);
-  flags.add("ent_coef", "Weigth of entropy loss.", &config.ent_coef);
-  flags.add("vf_coef", "Weigth of value loss.", &config.vf_coef);
-  flags.add("max_grad_norm", "Factor for gradient clipping.", &config.max_grad_norm);
-  flags.add("adam_eps", "Epsilon of adam.", &config.adam_eps);
-  flags.add("lr_schedule", "Learning rate schedule. Options: linear, none", &config.lr_schedule);
-  flags.add("clip_actions", "Whether to clip action into the valid range.", &config.clip_actions);
-  flags.add_list("gpu_ids", "The ids of the GPUs used for training. Usage: --gpu_ids 0 --gpu_ids 1 ...", &gpu_ids_given);
-  flags.add("rdzv_addr", "IP adress of master node. Default: localhost", &config.rdzv_addr);
-  flags.add("tcp_store_port", "Port for the TCP store. Default: 29500", &config.tcp_store_port);
-  flags.add("use_dd_ppo_preempt", "Flag to toggle the dd_ppo pre-emption trick", &config.use_dd_ppo_preempt);
-  flags.add("dd_ppo_min_perc", "Percentage of env steps that need to finish before preemtion.", &config.dd_ppo_min_perc);
-  flags.add("dd_ppo_preempt_threshold", "Percentage of envs that need to finish before preemtion.",
-            &config.dd_ppo_preempt_threshold);
-  flags.add_list("ports", "Ports of the carla_gym wrapper to connect to, one per env. Usage: --ports 0 --ports 1 ...",
-                 &ports_given);
-  flags.add("beta_min_a_b_value", "Minimum value for a, b of the beta distribution", &config.beta_min_a_b_value);
-  flags.add("obs_num_channels", "Number of channels in the BEV image.", &config.obs_num_channels);
-  flags.add("image_encoder", "Which image cnn encoder to use. Either roach, roach_ln", &config.image_encoder);
-  flags.add("use_layer_norm", "Whether to use LayerNorm before ReLU in MLPs.", &config.use_layer_norm);
-  flags.add("use_layer_norm_policy_head", "Whether to also apply layernorm to the policy head.",
-            &config.use_layer_norm_policy_head);
-  flags.add("use_positional_encoding", "Whether to add positional encoding to the image (not built)",
-            &config.use_positional_encoding);
-  flags.add("obs_num_measurements", "Number of scalar measurements in observation.", &config.obs_num_measurements);
-  flags.add("bev_semantics_width", "Numer of pixels the bev_semantics is wide", &config.bev_semantics_width);
-  flags.add("bev_semantics_height", "Numer of pixels the bev_semantics is high", &config.bev_semantics_height);
-  flags.add("num_value_measurements", "Number of measurements exclusive to the value head.",
-            &config.num_value_measurements);
-  flags.add("team_code_folder", "Path to the team_code folder where env_agent.py is (the comm_files root).",
-            &config.team_code_folder);
-  flags.add("load_file", "Path to an agent model to resume training from. If None no file will be loaded.",
-            &config.load_file);
-  flags.add("logdir", "Folder of the experiment folders", &config.logdir);
-  flags.add("exp_name", "Name of the experiment.", &config.exp_name);
-  flags.add("rdzv_file", "file used to exchange the RCCL id between ranks", &config.rdzv_file);
-  std::string collect_mode = "lockstep";
-  flags.add("collect_mode",
-            "How the envs of a process are stepped. Options: lockstep (one batched forward per step, envs one after "
-            "the other), threads (one thread and one batch-1 forward per env)",
-            &collect_mode);
-  try {
-    flags.parse(argc, argv);
-    if (collect_mode != "lockstep" && collect_mode != "threads")
-      throw ParseError("Option 'collect_mode' must be lockstep or threads. Chosen option: " + collect_mode);
-    if (config.team_code_folder.empty()) throw ParseError("Option 'team_code_folder' is required");
-  } catch (const HelpRequested&) {
-    flags.print_help(std::cout);
+  // 0: run, 1: help shown, 2: refused
+  auto parse_args = [&]() {
+    Flags flags;
+    ports_given.clear();
+    gpu_ids_given.clear();
+    config.add_flags(flags, &ports_given, &gpu_ids_given);
+    try {
+      flags.parse(argc, argv);
+      if (config.collect_mode != "lockstep" && config.collect_mode != "threads")
+        throw ParseError("Option 'collect_mode' must be lockstep or threads. Chosen option: " + config.collect_mode);
+      if (config.team_code_folder.empty()) throw ParseError("Option 'team_code_folder' is required");
+    } catch (const HelpRequested&) {
+      flags.print_help(std::cout);
+      return 1;
+    } catch (const ParseError& e) {
+      std::cerr << e.what() << std::endl;
+      flags.print_help(std::cerr);
+      return 2;
+    }
     return 0;
-  } catch (const ParseError& e) {
-    std::cerr << e.what() << std::endl;
-    flags.print_help(std::cerr);
-    return 1;
-  }
-  // args.hxx value lists replace the default once a value is given here (one port per env is required anyway)
-  if (!ports_given.empty()) config.ports = ports_given;
-  if (!gpu_ids_given.empty()) config.gpu_ids = gpu_ids_given;
+  };
+  if (const int rc = parse_args()) return rc - 1;
 
-  // the counters of an earlier run (:93-99: the folder's config.json, then the arguments again)
+  // an earlier run (:90-99): every key of the folder's config.json, then the arguments again on top.
+  // ports, gpu_ids and team_code_folder are not in the file (or empty there) and come from the arguments.
   int start_step = 0;
   if (config.load_file != "None") {
     const fs::path lf(config.load_file);
-    const FlatJson old = FlatJson::parse_file((lf.parent_path() / "config.json").string());
-    config.global_step = std::stol(old.raw("global_step"));
-    config.max_training_score = old.get_float("max_training_score", config.max_training_score);
-    config.best_iteration = old.get_int("best_iteration", 0);
+    try {
+      config.update_from_json(FlatJson::parse_file((lf.parent_path() / "config.json").string()));
+    } catch (const std::exception& e) {
+      std::cerr << "ac_ppo_carla: " << e.what() << std::endl;
+      return 1;
+    }
+    if (const int rc = parse_args()) return rc - 1;
     std::smatch match;
     const std::string name = lf.filename().string();
     if (std::regex_search(name, match, std::regex("(\\d+)(?=\\.pth)"))) {
@@ -279,6 +152,24 @@ int main(int argc, const char** argv) {
       std::cout << "Start training from step: " << start_step << std::endl;
     }
   }
+  // args.hxx value lists replace the default once a value is given here (one port per env is required anyway)
+  if (!ports_given.empty()) config.ports = ports_given;
+  if (!gpu_ids_given.empty()) config.gpu_ids = gpu_ids_given;
+  const std::string& collect_mode = config.collect_mode;
+  // :175-197. Collection and training both run on the agent's device in this build.
+  for (int k = 0; k < 2; ++k) {
+    const std::string& dev = k ? config.train_device : config.collect_device;
+    if (dev == "gpu") continue;
+    if (dev == "cpu") {
+      std::cerr << (k ? "train_device" : "collect_device") << " cpu: CPU mode is not built (DESIGN §7); use gpu"
+                << std::endl;
+      return k ? 3 : 2;
+    }
+    if (k) std::cerr << "Unsupported train device selected. Options: cpu, gpu. Selected device: " << dev << std::endl;
+    else std::cerr << "Unsupported Collect device selected. Options: cpu, gpu. Selected Device: " << dev << std::endl;
+    return k ? 3 : 2;
+  }
+  if (config.debug) std::cerr << "debug 1 is forwarded to the gyms; the trainer's OpenCV view is not built" << std::endl;
   config.derive(world_size);
   if (config.num_envs_per_proc <= 0 || config.num_envs % world_size != 0) {
     std::cerr << "num_envs must be a positive multiple of the number of ranks\n";
@@ -381,6 +272,11 @@ int main(int argc, const char** argv) {
       p0 = init_carla_params(L, config.seed, envs[0]->get_action_space_max(), envs[0]->get_action_space_min());
     }
     check(ppo_carla_load_params(agent, p0.data(), L.P), "ppo_carla_load_params");
+    // :246 Adam(lr).eps(adam_eps).weight_decay(weight_decay).betas(beta_1, beta_2), the fp32 fields widened.
+    // At the defaults the agent keeps its exact (0.9, 0.999, 0) and the default kernel.
+    if (config.beta_1 != 0.9f || config.beta_2 != 0.999f || config.weight_decay != 0.0f)
+      check(ppo_carla_set_adam(agent, (double)config.beta_1, (double)config.beta_2, (double)config.weight_decay),
+            "ppo_carla_set_adam");
     if (world_size > 1) {  // the RCCL id travels through a file, as in ac_ppo_continuous_action
       const std::string path = config.rdzv_file.empty() ? "/tmp/ppo_carla_rdzv_" + std::to_string(config.tcp_store_port) + ".id"
                                                         : config.rdzv_file;
@@ -413,9 +309,19 @@ int main(int argc, const char** argv) {
       const std::string opt_path = std::regex_replace(config.load_file, std::regex("model_"), "optimizer_");
       std::vector<float> m(L.P), v(L.P);
       long step = 0;
-      check(ppo_carla_pth_load_adam2(&L, opt_path.c_str(), m.data(), v.data(), L.P, &step, nullptr, nullptr),
+      double b1 = 0.0, b2 = 0.0, wd = 0.0, c1 = 0.0, c2 = 0.0, cwd = 0.0;
+      check(ppo_carla_pth_load_adam3(&L, opt_path.c_str(), m.data(), v.data(), L.P, &step, nullptr, nullptr, &b1, &b2,
+                                     &wd),
             "torch::load of the optimizer");
       check(ppo_carla_load_adam(agent, m.data(), v.data(), L.P, step), "ppo_carla_load_adam");
+      // torch::load(optimizer) assigns the saved options to the optimizer: the archive's betas and weight
+      // decay replace the configured ones (the learning rate is set per iteration, eps stays adam_eps)
+      check(ppo_carla_get_adam(agent, &c1, &c2, &cwd), "ppo_carla_get_adam");
+      if (b1 != c1 || b2 != c2 || wd != cwd) {
+        std::cout << "Optimizer options from " << opt_path << " replace the configured ones: betas (" << b1 << ", "
+                  << b2 << "), weight_decay " << wd << std::endl;
+        check(ppo_carla_set_adam(agent, b1, b2, wd), "ppo_carla_set_adam");
+      }
       if (rank == 0) logger->add_scalar("charts/restart", (int)config.global_step, 1.0);
     }
     if (rank == 0) std::cout << "Number of parameters in model: " << (L.P - 2) << std::endl;
@@ -634,6 +540,8 @@ int main(int argc, const char** argv) {
       check(ppo_carla_rollout_train(roll, &tc, lrnow, num_train_steps_per_env, nullptr, &st, &avg_clipfrac),
             "ppo_carla_rollout_train");
       config.latest_iteration = iteration;
+      float returns_mean = 0.0f;  // :626-658, :701: a collective, so every rank calls it
+      check(ppo_carla_rollout_returns_mean(roll, num_train_steps_per_env, &returns_mean), "ppo_carla_rollout_returns_mean");
 
       if (rank == 0) {  // :661-705
         char mf[64], of[64];
@@ -655,6 +563,7 @@ int main(int argc, const char** argv) {
         logger->add_scalar("losses/old_approx_kl", gs, st.old_approx_kl);
         logger->add_scalar("losses/approx_kl", gs, st.approx_kl);
         logger->add_scalar("losses/clipfrac", gs, avg_clipfrac);
+        logger->add_scalar("losses/discounted_returns", gs, returns_mean);
         logger->add_scalar("charts/SPS", gs, sps);
         logger->add_scalar("charts/restart", gs, 0.0);
       }

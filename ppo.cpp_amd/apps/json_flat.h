@@ -1,6 +1,7 @@
 // apps/json_flat.h — reader for the flat config.json the CaRL tools write and read
 // (carla_config.h:379-497 to_json / update_from_json with json_spirit): a top-level object whose
-// values are numbers, strings, booleans, null, or arrays / objects (kept as raw text). No LibTorch,
+// values are numbers, strings, booleans, null, or arrays / objects (kept as raw text); keys are any JSON
+// string ("py/object", the class tag the reference writes first, is one). No LibTorch,
 // no json_spirit; enough for GlobalConfig-style files.
 #pragma once
 

@@ -39,6 +39,8 @@ struct ppo_carla : CarlaFwdBufs, CarlaGradBufs {
   size_t part_floats = 0;
   float* small = nullptr;  // scalars, tensor table and norm slices (carla_train_init)
   long step = 0;
+  // Adam options (ppo_carla_set_adam): exactly (0.9, 0.999, 0) launches k_carla_adam, anything else k_carla_adam_opt
+  double beta1 = 0.9, beta2 = 0.999, weight_decay = 0.0;
   // conv1 / conv2 kernels: 2 packed conv1 taps (k_conv_img3), 1 LDS-staged (k_conv_img2 and the staged
   // wgrad / dgrad kernels), 0 generic (create option conv1=packed|staged|generic; PPO_CARLA_CONV1 in the
   // diagnostic build). The backward's staged kernels run for 1 and 2.
@@ -641,6 +643,64 @@ __global__ __launch_bounds__(256) void k_carla_adam(CarlaAdamArgs a) {
   a.P[p] = a.P[p] - a.step_size * (m / (sqrtf(v) / a.sbc2 + a.eps));
 }
 
+// Adam with the optimizer's options as arguments (ppo_carla_set_adam): LibTorch's Adam::step after
+// clip_grad_norm_, with coupled L2 (g += wd * p before the moments; not AdamW). k_carla_adam keeps the
+// options (0.9, 0.999, 0) compiled in and stays the launch for exactly those.
+struct CarlaAdamOptArgs {
+  float *P, *G, *m, *v;
+  long begin, n;        // trainable range [begin, begin + n)
+  long head, nvec;      // scalar elements before the first 16-byte boundary, then float4 groups, then the rest
+  const float* clip;    // {total, coef} from k_carla_tsum
+  float step_size, sbc2, eps;
+  float b1, omb1, b2, omb2, wd;  // (float)beta, (float)(1.0 - beta), (float)weight_decay
+};
+
+__device__ __forceinline__ void carla_adam_opt_one(const CarlaAdamOptArgs& a, float coef, float g, float& p, float& m,
+                                                   float& v) {
+  // One rounding per operation, in the order of include/ppo_carla.h: no contraction into fused multiply-adds,
+  // so m and v equal an fp32 restatement of Adam::step bit for bit. k_carla_adam compiles the same way for
+  // m and v (its literal betas make every product a plain multiply) and fuses only the parameter step's
+  // multiply into its subtraction.
+#pragma clang fp contract(off)
+  float gv = g * coef;
+  gv = gv + a.wd * p;
+  m = m * a.b1 + gv * a.omb1;
+  v = v * a.b2 + gv * gv * a.omb2;
+  p = p - a.step_size * (m / (sqrtf(v) / a.sbc2 + a.eps));
+}
+
+// An element-wise stream: thread i < nvec owns the float4 group at begin + head + 4 i (16-byte aligned:
+// every array is a hipMalloc base plus the same offset), the threads after them one element each of the
+// head and of the tail. Plain loads and stores, every element written by exactly one thread.
+__global__ __launch_bounds__(256) void k_carla_adam_opt(CarlaAdamOptArgs a) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const float coef = a.clip[1];
+  if (i < a.nvec) {
+    const long p = a.begin + a.head + 4 * i;
+    const float4 g4 = *reinterpret_cast<const float4*>(a.G + p);
+    float4 p4 = *reinterpret_cast<const float4*>(a.P + p);
+    float4 m4 = *reinterpret_cast<const float4*>(a.m + p);
+    float4 v4 = *reinterpret_cast<const float4*>(a.v + p);
+    carla_adam_opt_one(a, coef, g4.x, p4.x, m4.x, v4.x);
+    carla_adam_opt_one(a, coef, g4.y, p4.y, m4.y, v4.y);
+    carla_adam_opt_one(a, coef, g4.z, p4.z, m4.z, v4.z);
+    carla_adam_opt_one(a, coef, g4.w, p4.w, m4.w, v4.w);
+    *reinterpret_cast<float4*>(a.m + p) = m4;
+    *reinterpret_cast<float4*>(a.v + p) = v4;
+    *reinterpret_cast<float4*>(a.P + p) = p4;
+    return;
+  }
+  long k = i - a.nvec;  // the k-th scalar element: the head first, then the tail
+  if (k >= a.n - 4 * a.nvec) return;
+  if (k >= a.head) k += 4 * a.nvec;
+  const long p = a.begin + k;
+  float pv = a.P[p], mv = a.m[p], vv = a.v[p];
+  carla_adam_opt_one(a, coef, a.G[p], pv, mv, vv);
+  a.m[p] = mv;
+  a.v[p] = vv;
+  a.P[p] = pv;
+}
+
 }  // namespace
 
 // the largest wgrad partial buffer any layer needs at max_batch rows
@@ -818,10 +878,20 @@ extern "C" int ppo_carla_update(ppo_carla_t* c, const ppo_carla_train_config* tc
                      toff + PPO_CARLA_MAX_TENSORS2, sm + kSmallNorm);
   hipLaunchKernelGGL(k_carla_tsum, dim3(1), dim3(64), 0, s, sm + kSmallNorm, L.ntensors, tc->max_grad_norm, sm + 70);
   c->step += 1;
-  const double bc1 = 1.0 - std::pow(0.9, (double)c->step), bc2 = 1.0 - std::pow(0.999, (double)c->step);
-  CarlaAdamArgs ad{P, G, c->m, c->v, begin, L.P - begin, sm + 70, (float)((double)lr / bc1), (float)std::sqrt(bc2),
-                   tc->adam_eps};
-  hipLaunchKernelGGL(k_carla_adam, dim3((unsigned)((L.P - begin + 255) / 256)), dim3(256), 0, s, ad);
+  if (c->beta1 == 0.9 && c->beta2 == 0.999 && c->weight_decay == 0.0) {
+    const double bc1 = 1.0 - std::pow(0.9, (double)c->step), bc2 = 1.0 - std::pow(0.999, (double)c->step);
+    CarlaAdamArgs ad{P, G, c->m, c->v, begin, L.P - begin, sm + 70, (float)((double)lr / bc1), (float)std::sqrt(bc2),
+                     tc->adam_eps};
+    hipLaunchKernelGGL(k_carla_adam, dim3((unsigned)((L.P - begin + 255) / 256)), dim3(256), 0, s, ad);
+  } else {  // ppo_carla_set_adam: the options as arguments (torch/optim/adam.cpp Adam::step)
+    const double bc1 = 1.0 - std::pow(c->beta1, (double)c->step), bc2 = 1.0 - std::pow(c->beta2, (double)c->step);
+    const long n = L.P - begin, head = std::min<long>((4 - begin % 4) % 4, n), nvec = (n - head) / 4;
+    CarlaAdamOptArgs ad{P, G, c->m, c->v, begin, n, head, nvec, sm + 70, (float)((double)lr / bc1),
+                        (float)std::sqrt(bc2), tc->adam_eps, (float)c->beta1, (float)(1.0 - c->beta1),
+                        (float)c->beta2, (float)(1.0 - c->beta2), (float)c->weight_decay};
+    const long threads = nvec + (n - 4 * nvec);
+    hipLaunchKernelGGL(k_carla_adam_opt, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ad);
+  }
   hipLaunchKernelGGL(k_carla_stats, dim3(1), dim3(256), 0, s, c->rowstat, n, sm + 64);
   if (hipGetLastError() != hipSuccess) return ppo_fail("ppo_carla_update: launch failed", -2);
   if (int mrc = carla_params_mark(c, s)) return mrc;  // act lanes read the parameters after this step
@@ -887,6 +957,65 @@ extern "C" int ppo_carla_load_adam(ppo_carla_t* c, const float* m_host, const fl
     return ppo_fail("ppo_carla_load_adam: copy failed", -2);
   c->step = step;
   return 0;
+}
+
+extern "C" int ppo_carla_set_adam(ppo_carla_t* c, double beta1, double beta2, double weight_decay) {
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+    return ppo_fail("ppo_carla_set_adam: beta1 and beta2 must be in [0, 1)", -1);
+  if (!(weight_decay >= 0.0) || !std::isfinite(weight_decay))
+    return ppo_fail("ppo_carla_set_adam: weight_decay must be finite and not negative", -1);
+  if (!c) return ppo_fail("ppo_carla_set_adam: null argument", -1);
+  c->beta1 = beta1;
+  c->beta2 = beta2;
+  c->weight_decay = weight_decay;
+  return 0;
+}
+
+extern "C" int ppo_carla_get_adam(const ppo_carla_t* c, double* beta1, double* beta2, double* weight_decay) {
+  if (!c || !beta1 || !beta2 || !weight_decay) return ppo_fail("ppo_carla_get_adam: null argument", -1);
+  *beta1 = c->beta1;
+  *beta2 = c->beta2;
+  *weight_decay = c->weight_decay;
+  return 0;
+}
+
+// test hook (ppo_carla.h): both Adam launches alone, timed with HIP events on the agent's stream
+extern "C" int ppo_carla_debug_adam_time(ppo_carla_t* c, int reps, double beta1, double beta2, double weight_decay,
+                                         float* us_default, float* us_opt) {
+  if (!c || !us_default || !us_opt || reps <= 0) return ppo_fail("ppo_carla_debug_adam_time: bad argument", -1);
+  if (hipSetDevice(c->device) != hipSuccess) return ppo_fail("ppo_carla_debug_adam_time: hipSetDevice failed", -2);
+  if (int rc = carla_train_init(c)) return rc;
+  const ppo_carla_layout2& L = c->L;
+  hipStream_t s = c->stream;
+  const float clip[2] = {0.0f, 1.0f};
+  if (hipMemcpyAsync(c->small + 70, clip, sizeof clip, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return ppo_fail("ppo_carla_debug_adam_time: copy failed", -2);
+  const long begin = 2, n = L.P - begin, head = std::min<long>((4 - begin % 4) % 4, n), nvec = (n - head) / 4;
+  CarlaAdamArgs ad{c->P, c->G, c->m, c->v, begin, n, c->small + 70, 3e-4f, 1.0f, 1e-5f};
+  CarlaAdamOptArgs ao{c->P, c->G, c->m, c->v, begin, n, head, nvec, c->small + 70, 3e-4f, 1.0f, 1e-5f,
+                      (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)weight_decay};
+  const unsigned gd = (unsigned)((n + 255) / 256), go = (unsigned)((nvec + (n - 4 * nvec) + 255) / 256);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
+    return ppo_fail("ppo_carla_debug_adam_time: hipEventCreate failed", -2);
+  float ms[2] = {0.0f, 0.0f};
+  bool ok = true;
+  for (int which = 0; which < 2 && ok; ++which) {
+    for (int i = -3; i < reps; ++i) {  // three warm-up launches
+      if (i == 0) ok = ok && hipEventRecord(e0, s) == hipSuccess;
+      if (which == 0) hipLaunchKernelGGL(k_carla_adam, dim3(gd), dim3(256), 0, s, ad);
+      else hipLaunchKernelGGL(k_carla_adam_opt, dim3(go), dim3(256), 0, s, ao);
+    }
+    ok = ok && hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+         hipEventElapsedTime(&ms[which], e0, e1) == hipSuccess && hipGetLastError() == hipSuccess;
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (!ok) return ppo_fail("ppo_carla_debug_adam_time: timing failed", -2);
+  *us_default = ms[0] * 1000.0f / (float)reps;
+  *us_opt = ms[1] * 1000.0f / (float)reps;
+  return carla_params_mark(c, s);
 }
 
 // ------------------------------------------------------------------------------------------

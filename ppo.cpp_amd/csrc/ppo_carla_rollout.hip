@@ -138,6 +138,23 @@ __global__ void k_carla_rollout_fin(const float* __restrict__ slots, int nslots,
   fin[7] = last[6];
 }
 
+// losses/discounted_returns (ac_ppo_carla.cpp:626-658, :701): out[0] = mean over j < B of ret[j % Bc], the
+// collected rows repeated and truncated to the full batch as the permutation is. One block, a fixed
+// order: thread t adds its rows j = t, t + 256, ... in that order, then a tree over the 256 partial sums.
+__global__ __launch_bounds__(256) void k_carla_returns_mean(const float* __restrict__ ret, long Bc, long B,
+                                                            float* __restrict__ out) {
+  __shared__ float red[256];
+  float q = 0.f;
+  for (long j = threadIdx.x; j < B; j += 256) q += ret[j % Bc];
+  red[threadIdx.x] = q;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = red[0] / (float)B;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -160,7 +177,7 @@ struct ppo_carla_rollout {
   float *mb_meas = nullptr, *mb_vmeas = nullptr, *mb_actions = nullptr, *mb_logp = nullptr, *mb_adv = nullptr,
         *mb_ret = nullptr, *mb_values = nullptr;
   int32_t* perms = nullptr;  // [update_epochs][B]
-  float* slots = nullptr;    // [update_epochs * num_minibatches][kCarlaStatSlot], then fin [8]
+  float* slots = nullptr;    // [update_epochs * num_minibatches][kCarlaStatSlot], then fin [8], then returns_mean [8]
   // act lanes (ppo_carla.h "act lanes"). lanes: created and destroyed under the exclusive flag only.
   // sync_ev: recorded after every gae / train; a lane's next act waits for it before it writes storage rows.
   ppo_carla_lane_t* lanes[PPO_CARLA_MAX_LANES] = {};
@@ -344,7 +361,8 @@ extern "C" int ppo_carla_rollout_create(ppo_carla_t* agent, const ppo_carla_roll
   bad |= r_alloc((void**)&r->mb_actions, uM * r->A * f);
   for (float** p : {&r->mb_logp, &r->mb_adv, &r->mb_ret, &r->mb_values}) bad |= r_alloc((void**)p, uM * f);
   bad |= r_alloc((void**)&r->perms, (size_t)cfg->update_epochs * uB * sizeof(int32_t));
-  bad |= r_alloc((void**)&r->slots, ((size_t)nslots + 1) * kCarlaStatSlot * f);
+  // the update slots, train's `fin` block, then ppo_carla_rollout_returns_mean's scalar
+  bad |= r_alloc((void**)&r->slots, ((size_t)nslots + 2) * kCarlaStatSlot * f);
   bad |= hipEventCreateWithFlags(&r->sync_ev, hipEventDisableTiming) == hipSuccess ? 0 : 1;
   // the zero fills above ran on the null stream; the agent's stream does not wait for it
   if (!bad && hipDeviceSynchronize() != hipSuccess) bad = 1;
@@ -524,6 +542,27 @@ extern "C" int ppo_carla_rollout_train(ppo_carla_rollout_t* r, const ppo_carla_t
     }
     if (mean_clipfrac) *mean_clipfrac = h[6];
   }
+  return 0;
+}
+
+extern "C" int ppo_carla_rollout_returns_mean(ppo_carla_rollout_t* r, int num_steps_collected, float* out) {
+  if (!r || !out) return ppo_fail("ppo_carla_rollout_returns_mean: null argument", -1);
+  if (num_steps_collected <= 0 || num_steps_collected > r->T)
+    return ppo_fail("ppo_carla_rollout_returns_mean: bad collected step count", -1);
+  ExclusiveGuard guard(r);
+  if (!guard.ok) return ppo_fail("ppo_carla_rollout_returns_mean: called while a lane call is inside the library", -1);
+  if (hipSetDevice(r->info.device) != hipSuccess)
+    return ppo_fail("ppo_carla_rollout_returns_mean: hipSetDevice failed", -2);
+  hipStream_t s = r->info.stream;
+  // the slot after train's `fin` block is free between calls: calls on one object are serial
+  float* slot = r->slots + ((size_t)r->cfg.update_epochs * r->cfg.num_minibatches + 1) * kCarlaStatSlot;
+  hipLaunchKernelGGL(k_carla_returns_mean, dim3(1), dim3(256), 0, s, r->ret, (long)num_steps_collected * r->E, r->B,
+                     slot);
+  if (hipGetLastError() != hipSuccess) return ppo_fail("ppo_carla_rollout_returns_mean: launch failed", -2);
+  if (int rc = ppo_carla_comm_allreduce(r->agent, slot, 1, 1)) return rc;  // :650 averaged over ranks
+  if (hipMemcpyAsync(out, slot, sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return ppo_fail("ppo_carla_rollout_returns_mean: copy failed", -2);
   return 0;
 }
 

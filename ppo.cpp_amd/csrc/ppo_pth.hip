@@ -333,3 +333,42 @@ extern "C" int ppo_carla_pth_load_adam2(const ppo_carla_layout2* L, const char* 
     return 0;
   });
 }
+
+// the same with the optimizer's betas and weight decay (ac_ppo_carla.cpp:246: Adam(lr).eps().weight_decay().betas())
+extern "C" int ppo_carla_pth_save_adam3(const ppo_carla_layout2* L, const float* m, const float* v, long step,
+                                        double lr, double eps, double beta1, double beta2, double weight_decay,
+                                        const char* path) {
+  if (!L || !m || !v || !path) return ppo_fail("ppo_carla_pth_save_adam3: null argument", -1);
+  if (step < 0) return ppo_fail("ppo_carla_pth_save_adam3: negative step", -1);
+  return guarded([&] {
+    const pth::Spec s = carla_spec2(*L);
+    if (!covers(s)) return ppo_fail("ppo_carla_pth_save_adam3: layout does not match the agent structure", -1);
+    pth::AdamOptions o;
+    o.lr = lr;
+    o.eps = eps;
+    o.beta1 = beta1;
+    o.beta2 = beta2;
+    o.weight_decay = weight_decay;
+    pth::save_adam(path, s, m, v, step, o);
+    return 0;
+  });
+}
+
+extern "C" int ppo_carla_pth_load_adam3(const ppo_carla_layout2* L, const char* path, float* m, float* v, long n,
+                                        long* step, double* lr_out, double* eps_out, double* beta1_out,
+                                        double* beta2_out, double* weight_decay_out) {
+  if (!L || !m || !v || !path || !step) return ppo_fail("ppo_carla_pth_load_adam3: null argument", -1);
+  if (n != L->P) return ppo_fail("ppo_carla_pth_load_adam3: n != layout P", -1);
+  return guarded([&] {
+    const pth::Spec s = carla_spec2(*L);
+    if (!covers(s)) return ppo_fail("ppo_carla_pth_load_adam3: layout does not match the agent structure", -1);
+    pth::AdamOptions o;
+    *step = pth::load_adam(path, s, m, v, &o);
+    if (lr_out) *lr_out = o.lr;
+    if (eps_out) *eps_out = o.eps;
+    if (beta1_out) *beta1_out = o.beta1;
+    if (beta2_out) *beta2_out = o.beta2;
+    if (weight_decay_out) *weight_decay_out = o.weight_decay;
+    return 0;
+  });
+}

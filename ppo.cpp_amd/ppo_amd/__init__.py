@@ -290,6 +290,14 @@ SYMBOLS = [
     ("ppo_carla_lane_reward", _I, [_VP, _I, _I, _F]),
     ("ppo_carla_lane_sync", _I, [_VP]),
     ("ppo_carla_debug_lane_in", _I, [_I, _I, _FP, _FP, _F, _F, _FP, _FP, _FP, _FP, _VP]),
+    ("ppo_carla_set_adam", _I, [_VP, C.c_double, C.c_double, C.c_double]),
+    ("ppo_carla_get_adam", _I, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("ppo_carla_debug_adam_time", _I, [_VP, _I, C.c_double, C.c_double, C.c_double, C.POINTER(_F), C.POINTER(_F)]),
+    ("ppo_carla_rollout_returns_mean", _I, [_VP, _I, C.POINTER(_F)]),
+    ("ppo_carla_pth_save_adam3", _I, [C.POINTER(CarlaLayout2), _FP, _FP, _L, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, C.c_char_p]),
+    ("ppo_carla_pth_load_adam3", _I, [C.POINTER(CarlaLayout2), C.c_char_p, _FP, _FP, _L, C.POINTER(_L)] +
+     [C.POINTER(C.c_double)] * 5),
 ]
 
 
@@ -423,6 +431,23 @@ def load_carla_adam_pth2(layout: CarlaLayout2, path):
     check(lib().ppo_carla_pth_load_adam2(C.byref(layout), os.fsencode(path), m.ctypes.data, v.ctypes.data, layout.P,
                                          C.byref(step), C.byref(lr), C.byref(eps)))
     return m, v, step.value, lr.value, eps.value
+
+
+def save_carla_adam_pth3(layout: CarlaLayout2, m, v, step, lr, eps, beta1, beta2, weight_decay, path):
+    """save_carla_adam_pth2 with the optimizer's betas and weight decay (CarlaAgent.set_adam)"""
+    m, v = _f32(m, layout.P), _f32(v, layout.P)
+    check(lib().ppo_carla_pth_save_adam3(C.byref(layout), m.ctypes.data, v.ctypes.data, int(step), float(lr),
+                                         float(eps), float(beta1), float(beta2), float(weight_decay),
+                                         os.fsencode(path)))
+
+
+def load_carla_adam_pth3(layout: CarlaLayout2, path):
+    """torch::load(optimizer, path) -> (exp_avg, exp_avg_sq, step, lr, eps, beta1, beta2, weight_decay)"""
+    m, v = np.empty(layout.P, np.float32), np.empty(layout.P, np.float32)
+    step, o = C.c_long(0), [C.c_double(0) for _ in range(5)]
+    check(lib().ppo_carla_pth_load_adam3(C.byref(layout), os.fsencode(path), m.ctypes.data, v.ctypes.data, layout.P,
+                                         C.byref(step), *[C.byref(x) for x in o]))
+    return (m, v, step.value) + tuple(x.value for x in o)
 
 
 def obs_norm(env_id):
@@ -874,6 +899,24 @@ class CarlaAgent:
         m, v = np.ascontiguousarray(m, np.float32), np.ascontiguousarray(v, np.float32)
         check(lib().ppo_carla_load_adam(self._h, m.ctypes.data, v.ctypes.data, m.size, int(step)))
 
+    def set_adam(self, beta1=0.9, beta2=0.999, weight_decay=0.0):
+        """The optimizer's betas and (coupled L2) weight decay; they persist across updates, train calls and
+        load_adam. Exactly (0.9, 0.999, 0) keeps the default kernel and its bits."""
+        check(lib().ppo_carla_set_adam(self._h, float(beta1), float(beta2), float(weight_decay)))
+
+    def adam_options(self):
+        """(beta1, beta2, weight_decay)"""
+        o = [C.c_double(0) for _ in range(3)]
+        check(lib().ppo_carla_get_adam(self._h, *[C.byref(x) for x in o]))
+        return tuple(x.value for x in o)
+
+    def debug_adam_time(self, reps=200, beta1=0.8, beta2=0.99, weight_decay=0.01):
+        """(k_carla_adam, k_carla_adam_opt) microseconds per launch (HIP events); steps the agent's state"""
+        a, b = C.c_float(0), C.c_float(0)
+        check(lib().ppo_carla_debug_adam_time(self._h, int(reps), float(beta1), float(beta2), float(weight_decay),
+                                              C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def comm_init(self, uid: bytes, rank=0, world=1):
         """Attach an RCCL communicator (ac_ppo_carla.cpp:561-616 data parallelism); uid from
         Agent.comm_unique_id()."""
@@ -949,6 +992,14 @@ class CarlaRollout:
         d = st.as_dict()
         d["mean_clipfrac"] = mc.value
         return d
+
+    def returns_mean(self, num_steps_collected=None):
+        """losses/discounted_returns: the mean of the returns over the collected rows, repeated and truncated
+        to T * E, rank-averaged; one fixed-order device reduction"""
+        out = C.c_float(0)
+        check(lib().ppo_carla_rollout_returns_mean(
+            self._h, self.cfg.num_steps if num_steps_collected is None else num_steps_collected, C.byref(out)))
+        return out.value
 
     def buffer(self, name) -> DeviceArray:
         """the storage array `name` (CARLA_BUFFERS) as a DeviceArray view"""
