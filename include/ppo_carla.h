@@ -8,7 +8,7 @@
  * use_positional_encoding false (:117), obs_num_channels 15 (:58), bev 192 x 192 (:101-102),
  * obs_num_measurements 8 (:90), num_value_measurements 3 (:103), beta_min_a_b_value 1.0 (:56).
  *
- *   bev uint8 [N, C, 192, 192] / 255
+ *   bev uint8 [N, C, 192, 192] / 255            (not divided under use_positional_encoding, below)
  *     -> cnn: Conv(C,8,5,s2) ReLU Conv(8,16,5,s2) ReLU Conv(16,32,5,s2) ReLU
  *             Conv(32,64,3,s2) ReLU Conv(64,128,3,s2) ReLU Conv(128,256,3,s1) ReLU   -> [N, 1024]
  *     state_linear: Linear(8,256) ReLU Linear(256,256) ReLU on measurements         -> [N, 256]
@@ -32,7 +32,20 @@
  * ppo_carla_create2; their tensors are described by ppo_carla_layout2 (cnn.{3i} / cnn.{3i+1},
  * linear.{0,1,3,4}, ..., value_head.{0,1,3,4,6}). Everything above — ppo_carla_layout,
  * ppo_carla_create(_ex), the default agent's kernels and results — is unchanged by them.
- * "roach_ln2" and use_positional_encoding are not built.
+ * "roach_ln2" is not built.
+ *
+ * use_positional_encoding (:38-42, :222-236) is the pos_enc argument of ppo_carla_create3: cnn.0 takes
+ * C + 2 channels, plane C = linspace(-1, 1, IH)[row], plane C + 1 = linspace(-1, 1, IW)[col]
+ * (meshgrid "ij"). The two planes are never built: they are the same for every sample and constant along
+ * one axis each, so their part of conv1's pre-activation is rowb[oc, oy] + colb[oc, ox], two small tables
+ * computed from cnn.0.weight in every forward and added with the bias, and their weight gradient comes
+ * from the row and column sums of conv1's pre-activation gradient (ppo_carla_pos.hip). A bev row stays
+ * C * IH * IW bytes everywhere. THE BEV IS NOT NORMALISED WHEN THE SWITCH IS ON: the reference computes
+ * bev / 255 and then overwrites it with concatenate({bev_semantics, grid0, grid1}, 1), whose first
+ * operand is the raw uint8 tensor, promoted to fp32, so conv1 sees 0..255 and not 0..1. This is
+ * reproduced as written: a checkpoint trained by the reference expects it. The inference server
+ * (ppo_carla_inference) still refuses the switch; a positional checkpoint is served through
+ * ppo_carla_forward, the Python binding, or the reference's own server (the .pth is LibTorch's).
  *
  * The training iteration around the agent (ac_ppo_carla.cpp:284-621) is a second handle,
  * ppo_carla_rollout_t, created from an agent: [T, E] storage of the dict observations on the device,
@@ -177,16 +190,22 @@ static inline long ppo_carla__add2(ppo_carla_layout2* L, long* cur, long n, int 
 }
 
 /* Returns 0; -1 as ppo_carla_layout_init; -2 if arch->encoder_ln is set with a bev other than
- * 192 x 192 (the reference hard-codes roach_ln's LayerNorm shapes, carla_model.h:45-62). arch NULL
- * = all zero. */
-static inline int ppo_carla_layout2_init(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
-                                         const ppo_carla_arch* arch) {
+ * 192 x 192 (the reference hard-codes roach_ln's LayerNorm shapes, carla_model.h:45-62); -3 for a
+ * pos_enc other than 0 or 1. arch NULL = all zero.
+ *
+ * pos_enc = 1 is use_positional_encoding (carla_model.h:38-42): cnn.0 is built with C + 2 input
+ * channels, so conv_ic[0] == C + 2, cnn.0.weight is [8, C + 2, 5, 5] and every later offset moves by
+ * 8 * 2 * 25 = 400. C stays the image's channel count; conv_ic[0] - C (0 or 2) IS the switch, no other
+ * field records it. No tensor is added or renamed. */
+static inline int ppo_carla_layout2_init_pos(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
+                                             const ppo_carla_arch* arch, int pos_enc) {
   static const int oc[PPO_CARLA_NCONV] = {8, 16, 32, 64, 128, 256};
   static const int ks[PPO_CARLA_NCONV] = {5, 5, 5, 3, 3, 3};
   static const int st[PPO_CARLA_NCONV] = {2, 2, 2, 2, 2, 1};
   long cur = 0;
-  int i, h = IH, w = IW, ic = C;
+  int i, h = IH, w = IW, ic = C + (pos_enc ? 2 : 0);
   const int eln = arch && arch->encoder_ln, mln = arch && arch->mlp_ln, pln = mln && arch->policy_ln;
+  if (pos_enc != 0 && pos_enc != 1) return -3;
   if (C <= 0 || IH <= 0 || IW <= 0 || NM <= 0 || NV < 0 || A <= 0) return -1;
   if (eln && (IH != 192 || IW != 192)) return -2;
   L->C = C; L->IH = IH; L->IW = IW; L->NM = NM; L->NV = NV; L->A = A;
@@ -227,9 +246,19 @@ static inline int ppo_carla_layout2_init(ppo_carla_layout2* L, int C, int IH, in
   return 0;
 }
 
+static inline int ppo_carla_layout2_init(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
+                                         const ppo_carla_arch* arch) {
+  /* not "return f(...)": tests/test_capi_cpu.py reads a line of that form as the declaration of an export */
+  const int rc = ppo_carla_layout2_init_pos(L, C, IH, IW, NM, NV, A, arch, 0);
+  return rc;
+}
+
 /* the exported form of ppo_carla_layout2_init (bindings); the message names the reason */
 int ppo_carla_layout2_fill(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
                            const ppo_carla_arch* arch);
+/* the exported form of ppo_carla_layout2_init_pos; pos_enc = 0 fills what ppo_carla_layout2_fill fills */
+int ppo_carla_layout2_fill_pos(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
+                               const ppo_carla_arch* arch, int pos_enc);
 /* named_parameters() name of tensor t ("cnn.1.weight", ...) into buf (NUL-terminated, truncated to
  * len); returns 0, -1 for a bad index or buffer */
 int ppo_carla_tensor_name(const ppo_carla_layout2* L, int t, char* buf, int len);
@@ -282,11 +311,20 @@ int ppo_carla_get_layout(const ppo_carla_t* c, ppo_carla_layout* out);
 /* ppo_carla_create_ex with an architecture (arch NULL = all zero = ppo_carla_create_ex). Refused
  * before any HIP call: encoder_ln with a bev other than 192 x 192, and an explicit tail=fused or
  * tail=staged with any LayerNorm (such an agent always runs the per-layer forward, one k_carla_ln
- * after each normalised layer). roach_ln2 and use_positional_encoding are not built.
+ * after each normalised layer). roach_ln2 is not built; use_positional_encoding is ppo_carla_create3's.
  * ppo_carla_get_layout2 serves every agent (the default one's offsets are ppo_carla_layout's);
- * ppo_carla_get_layout fails on a LayerNorm agent, whose tensors it cannot describe. */
+ * ppo_carla_get_layout fails on a LayerNorm agent and on a positional one, whose tensors it cannot
+ * describe. */
 int ppo_carla_create2(const ppo_carla_config* cfg, const ppo_carla_arch* arch, int device, const char* options,
                       ppo_carla_t** out);
+/* ppo_carla_create2 with use_positional_encoding (pos_enc = 1; see the head of this file). pos_enc = 0 IS
+ * ppo_carla_create2: the same kernels, launches and bits. cfg->obs_channels stays the image's channel
+ * count; the layout says conv_ic[0] == obs_channels + 2. Every conv1= and conv1_mfma= option is carried:
+ * each conv1 kernel reads the image channels of the wider filters, takes the image scale (1 instead of
+ * 1 / 255) as an argument and adds the two tables in its epilogue. Refused before any HIP call, besides
+ * what ppo_carla_create2 refuses: a pos_enc other than 0 or 1. */
+int ppo_carla_create3(const ppo_carla_config* cfg, const ppo_carla_arch* arch, int pos_enc, int device,
+                      const char* options, ppo_carla_t** out);
 int ppo_carla_get_layout2(const ppo_carla_t* c, ppo_carla_layout2* out);
 /* host floats in named_parameters() order (torch::load of a model_*.pth, ac_ppo_carla.cpp) */
 int ppo_carla_load_params(ppo_carla_t* c, const float* host, long n);
@@ -368,6 +406,20 @@ int ppo_carla_debug_ln_forward(int n, int F, const float* z, long in_stride, con
 int ppo_carla_debug_ln_backward(int n, int F, const float* z, long in_stride, const float* gamma, const float* stat,
                                 const float* y, long out_stride, const float* dy, float* dz, float* dgamma,
                                 float* dbeta, void* stream);
+
+/* ---- test hooks: positional encoding (ppo_carla_pos.hip) ------------------------------------------
+ * pos_grid: host[0..n) = the library's torch.linspace(-1, 1, n) in fp32 (host only, no HIP call).
+ * pos_bias: the agent's table launch on caller arrays (device pointers): rowb [OC][OH], colb [OC][OW]
+ * from W [OC][IC_total][K][K], whose planes C and C + 1 are the two coordinate planes' weights
+ * (OH = (IH - K) / S + 1, OW likewise).
+ * pos_wgrad: the agent's reduction (k_pos_rq) and finish (k_pos_wfin) on dz [n][OC][OH][OW] (dense,
+ * device): dw_pos [OC][2][K][K], with partial-sum buffers sized for max_n >= n as an agent's are for
+ * max_batch. Both synchronise the stream. */
+int ppo_carla_debug_pos_grid(int n, float* host);
+int ppo_carla_debug_pos_bias(int OC, int IC_total, int C, int K, int S, int IH, int IW, const float* W_dev,
+                             float* rowb_dev, float* colb_dev, void* stream);
+int ppo_carla_debug_pos_wgrad(int n, int max_n, int OC, int OH, int OW, int K, int S, int IH, int IW,
+                              const float* dz_dev, float* dw_pos_dev, void* stream);
 
 /* ---- data parallelism (ac_ppo_carla.cpp:243, 561-616; torchfort::Comm, distributed.cpp:81-224) ----
  * One RCCL communicator per agent; id from ppo_comm_unique_id (ppo_hip.h), PPO_COMM_ID_BYTES bytes.

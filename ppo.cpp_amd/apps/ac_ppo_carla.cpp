@@ -28,11 +28,14 @@
 // table for the flags, the JSON sent to the gyms on <port>.conf_lock, config.json and its reader). The
 // reward / rendering / termination options are stored and forwarded, as in the reference's trainer; beta_1,
 // beta_2 and weight_decay reach the device optimizer (ppo_carla_set_adam) and the optimizer archive. Not
-// built: collect_device / train_device cpu, the OpenCV view of --debug 1, roach_ln2, use_positional_encoding.
+// built: collect_device / train_device cpu, the OpenCV view of --debug 1, roach_ln2. use_positional_encoding
+// creates the agent through ppo_carla_create3 (cnn.0 with obs_num_channels + 2 input channels on the
+// un-normalised bev, include/ppo_carla.h); checkpoints, config.json and the gyms' JSON carry the switch.
 #include <hip/hip_runtime.h>
 
 #include <deque>
 #include <iomanip>
+#include <map>
 #include <numeric>
 #include <regex>
 #include <set>
@@ -56,12 +59,23 @@ static int env_int(const char* a, const char* b, int def) {
   return def;
 }
 
-// LibTorch's default initialisation, which the reference's Agent keeps (carla_model.h never applies
-// _weights_init): Conv2d / Linear weight and bias U(+-1 / sqrt(fan_in)) (kaiming_uniform_(a = sqrt(5))),
-// LayerNorm weight 1 / bias 0; action_space_high / _low from the env.
+// Fresh parameters. Linear: LibTorch's default, weight and bias U(+-1 / sqrt(fan_in))
+// (kaiming_uniform_(a = sqrt(5))), as the reference's Agent keeps it; LayerNorm weight 1 / bias 0;
+// action_space_high / _low from the env. Conv2d: the reference wraps every convolution in _weights_init
+// (carla_model.h:45-76, :555-560): xavier_uniform_ with gain sqrt(2), U(+-sqrt(2) * sqrt(6 / (fan_in + fan_out))),
+// fan_in = IC * K * K, fan_out = OC * K * K, and bias 0.1. A positional agent's convolutions are drawn that
+// way, cnn.0 with IC = obs_num_channels + 2 (+-0.139 at 15 channels). The agents without the switch keep what
+// this trainer has always drawn for them, the Linear rule with fan_in = IC * K * K for the convolutions too:
+// that departs from the reference and is left for a change of its own, since it alters every existing run.
 static std::vector<float> init_carla_params(const ppo_carla_layout2& L, int seed, float hi, float lo) {
   std::vector<float> p(L.P, 0.0f);
   std::mt19937 rng((uint32_t)seed);
+  const bool reference_conv_init = L.conv_ic[0] != L.C;
+  std::map<long, float> xavier;  // conv weight offset -> bound
+  for (int i = 0; i < PPO_CARLA_NCONV; ++i) {
+    const float kk = (float)(L.conv_k[i] * L.conv_k[i]);
+    xavier[L.conv_w[i]] = std::sqrt(2.0f) * std::sqrt(6.0f / ((float)(L.conv_ic[i] + L.conv_oc[i]) * kk));
+  }
   std::set<long> ln;
   for (int i = 0; i < PPO_CARLA_NCONV; ++i) ln.insert(L.conv_g[i]);
   for (int i = 0; i < 2; ++i) {
@@ -73,6 +87,12 @@ static std::vector<float> init_carla_params(const ppo_carla_layout2& L, int seed
     const long w = L.t_off[t], nw = L.t_len[t], b = L.t_off[t + 1], nb = L.t_len[t + 1];
     if (ln.count(w)) {
       std::fill(p.begin() + w, p.begin() + w + nw, 1.0f);
+      continue;
+    }
+    if (reference_conv_init && xavier.count(w)) {
+      std::uniform_real_distribution<float> u(-xavier[w], xavier[w]);
+      for (long i = 0; i < nw; ++i) p[w + i] = u(rng);
+      std::fill(p.begin() + b, p.begin() + b + nb, 0.1f);
       continue;
     }
     const float bound = 1.0f / std::sqrt((float)(nw / nb));
@@ -186,10 +206,6 @@ int main(int argc, const char** argv) {
               << std::endl;
     return 1;
   }
-  if (config.use_positional_encoding) {
-    std::cerr << "use_positional_encoding is not built (carla_model.h:39-42, :226-234)" << std::endl;
-    return 1;
-  }
   if ((size_t)local_rank >= config.gpu_ids.size()) {
     std::cerr << "local rank " << local_rank << " has no entry in --gpu_ids (" << config.gpu_ids.size()
               << " given): pass one --gpu_ids per local rank\n";
@@ -261,7 +277,8 @@ int main(int argc, const char** argv) {
     cc.seed = (uint64_t)config.seed;
     cc.rank = rank;
     ppo_carla_t* agent = nullptr;
-    check(ppo_carla_create2(&cc, &arch, device, nullptr, &agent), "ppo_carla_create2");
+    check(ppo_carla_create3(&cc, &arch, config.use_positional_encoding ? 1 : 0, device, nullptr, &agent),
+          "ppo_carla_create3");
     ppo_carla_layout2 L;
     check(ppo_carla_get_layout2(agent, &L), "ppo_carla_get_layout2");
     std::vector<float> p0;

@@ -267,7 +267,7 @@ struct GlobalConfig {
         R("beta_2", &beta_2, "Adam's second-moment decay"),
         B("render_speed_lines", &render_speed_lines, "gym: speed lines on moving objects"),
         B("use_new_stop_sign_detector", &use_new_stop_sign_detector, "gym: stop-sign check that lane changes cannot dodge"),
-        B("use_positional_encoding", &use_positional_encoding, "Positional encoding channels (not built)"),
+        B("use_positional_encoding", &use_positional_encoding, "1: two coordinate channels (linspace(-1, 1) by row and by column) beside the bev, which is then not divided by 255"),
         B("use_ttc", &use_ttc, "gym: time-to-collision term in the reward"),
         I("ttc_resolution", &ttc_resolution, nullptr),
         I("ttc_penalty_ticks", &ttc_penalty_ticks, nullptr),

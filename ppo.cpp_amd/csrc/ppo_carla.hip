@@ -71,7 +71,15 @@ struct ppo_carla : CarlaFwdBufs, CarlaGradBufs {
   // LayerNorm agents: the column pass's chunk sums (carla_train_init)
   float* lnpart = nullptr;
   size_t lnpart_floats = 0;
+  // positional agents (L.conv_ic[0] == L.C + 2): the row / column sums of dZ1 per sample chunk (carla_train_init)
+  float* pospart = nullptr;
+  size_t pospart_floats = 0;
 };
+
+// use_positional_encoding: conv1's filters hold two more channels than the image has
+static inline bool carla_pos(const ppo_carla_layout2& L) { return L.conv_ic[0] != L.C; }
+// the channels convolution i reads from memory (conv1: the image's, also for a positional agent)
+static inline int carla_in_c(const ppo_carla_layout2& L, int i) { return i ? L.conv_ic[i] : L.C; }
 
 static int carla_alloc(float** p, size_t n) {
   if (hipMalloc((void**)p, (n ? n : 1) * sizeof(float)) != hipSuccess) return -2;
@@ -106,15 +114,27 @@ static void carla_net_init(const ppo_carla_layout2& L, CarlaNet* net) {
 // act[i - 1]) is contiguous; out / dz may be strided (conv6 writes columns 0..1023 of enc).
 static ConvArgs conv_args(const ppo_carla_layout2& L, int i, const float* P, const float* in_f, const uint8_t* in_u8,
                           float* out, long out_stride, int relu, int n, float* ksplit) {
-  return ConvArgs{in_f, in_u8, (long)L.conv_ic[i] * L.conv_ih[i] * L.conv_iw[i], L.conv_ic[i], L.conv_ih[i],
-                  L.conv_iw[i], P + L.conv_w[i], P + L.conv_b[i], out, out_stride, L.conv_oc[i], L.conv_oh[i],
-                  L.conv_ow[i], L.conv_k[i], L.conv_s[i], relu, n, ksplit, 0};
+  const int ic = carla_in_c(L, i);
+  ConvArgs a{in_f, in_u8, (long)ic * L.conv_ih[i] * L.conv_iw[i], ic, L.conv_ih[i],
+             L.conv_iw[i], P + L.conv_w[i], P + L.conv_b[i], out, out_stride, L.conv_oc[i], L.conv_oh[i],
+             L.conv_ow[i], L.conv_k[i], L.conv_s[i], relu, n, ksplit, 0};
+  if (i == 0 && carla_pos(L)) {  // the raw bytes against the image channels of the wider filters
+    a.wstride = L.conv_ic[0] * L.conv_k[0] * L.conv_k[0];
+    a.xscale = 1.0f;
+  }
+  return a;
 }
 static WgradArgs wgrad_args(const ppo_carla_layout2& L, int i, const float* dz, long dz_stride, const float* x_f,
                             const uint8_t* x_u8, int n, long group_bytes) {
-  return WgradArgs{dz, dz_stride, L.conv_oc[i], L.conv_oh[i] * L.conv_ow[i], L.conv_ow[i], x_f, x_u8,
-                   (long)L.conv_ic[i] * L.conv_ih[i] * L.conv_iw[i], L.conv_ic[i], L.conv_ih[i], L.conv_iw[i],
-                   L.conv_k[i], L.conv_s[i], n, L.conv_ic[i] * L.conv_k[i] * L.conv_k[i], 0, nullptr, group_bytes};
+  const int ic = carla_in_c(L, i);
+  WgradArgs a{dz, dz_stride, L.conv_oc[i], L.conv_oh[i] * L.conv_ow[i], L.conv_ow[i], x_f, x_u8,
+              (long)ic * L.conv_ih[i] * L.conv_iw[i], ic, L.conv_ih[i], L.conv_iw[i],
+              L.conv_k[i], L.conv_s[i], n, ic * L.conv_k[i] * L.conv_k[i], 0, nullptr, group_bytes};
+  if (i == 0 && carla_pos(L)) {
+    a.wstride = L.conv_ic[0] * L.conv_k[0] * L.conv_k[0];
+    a.xscale = 1.0f;
+  }
+  return a;
 }
 static DgradArgs dgrad_args(const ppo_carla_layout2& L, int i, const float* P, const float* dz, long dz_stride,
                             const float* x, float* dx, int n) {
@@ -150,6 +170,7 @@ int carla_fwd_alloc(const ppo_carla_t* c, size_t B, CarlaFwdBufs* fb) {
     if (m) rc |= carla_alloc(&fb->ksplit, m);
   }
   rc |= carla_alloc(&fb->c1w, (size_t)img3_blocks(L.C, L.conv_k[0]) * 256);
+  if (carla_pos(L)) rc |= carla_alloc(&fb->posb, (size_t)L.conv_oc[0] * (L.conv_oh[0] + L.conv_ow[0]));
   rc |= carla_alloc(reinterpret_cast<float**>(&fb->tail_bar), 1);
   fb->tail_count = 0;
   {  // pre-activation and statistics buffers of the normalised layers
@@ -172,7 +193,7 @@ int carla_fwd_alloc(const ppo_carla_t* c, size_t B, CarlaFwdBufs* fb) {
 
 void carla_fwd_free(CarlaFwdBufs* fb) {
   float* bufs[] = {fb->enc, fb->s1, fb->l1,   fb->feat,   fb->v1,  fb->v2,
-                   fb->val, fb->p1, fb->p2,   fb->hpre,   fb->ksplit, fb->c1w, reinterpret_cast<float*>(fb->tail_bar)};
+                   fb->val, fb->p1, fb->p2,   fb->hpre,   fb->ksplit, fb->c1w, fb->posb, reinterpret_cast<float*>(fb->tail_bar)};
   for (float* b : bufs)
     if (b) (void)hipFree(b);
   for (float* b : fb->act)
@@ -199,6 +220,7 @@ extern "C" int ppo_carla_destroy(ppo_carla_t* c) {
   for (float* b : c->dact)
     if (b) (void)hipFree(b);
   if (c->lnpart) (void)hipFree(c->lnpart);
+  if (c->pospart) (void)hipFree(c->pospart);
   if (c->params_ev) (void)hipEventDestroy(c->params_ev);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -215,7 +237,15 @@ extern "C" int ppo_carla_create_ex(const ppo_carla_config* cfg, int device, cons
 
 extern "C" int ppo_carla_create2(const ppo_carla_config* cfg, const ppo_carla_arch* arch, int device,
                                  const char* options, ppo_carla_t** out) {
+  return ppo_carla_create3(cfg, arch, 0, device, options, out);
+}
+
+extern "C" int ppo_carla_create3(const ppo_carla_config* cfg, const ppo_carla_arch* arch, int pos_enc, int device,
+                                 const char* options, ppo_carla_t** out) {
   if (!cfg || !out) return ppo_fail("ppo_carla_create: null argument", -1);
+  if (pos_enc != 0 && pos_enc != 1)
+    return ppo_fail("ppo_carla_create3: pos_enc must be 0 or 1 (use_positional_encoding), got " +
+                    std::to_string(pos_enc), -1);
   int conv_img = kConv1Auto;
   int tail_mode = 1;
   const char* tail_given = nullptr;
@@ -271,11 +301,14 @@ extern "C" int ppo_carla_create2(const ppo_carla_config* cfg, const ppo_carla_ar
   if (any_ln) tail_mode = 2;
   if (int rc = ppo_runtime_check()) return rc;
   ppo_carla_layout2 L{};  // unused table entries stay zero
-  if (ppo_carla_layout2_init(&L, cfg->obs_channels, cfg->bev_h, cfg->bev_w, cfg->num_measurements,
-                             cfg->num_value_measurements, cfg->action_dim, arch) != 0)
+  if (ppo_carla_layout2_init_pos(&L, cfg->obs_channels, cfg->bev_h, cfg->bev_w, cfg->num_measurements,
+                                 cfg->num_value_measurements, cfg->action_dim, arch, pos_enc) != 0)
     return ppo_fail("ppo_carla_create: the roach encoder needs a bev that ends at 256 x 2 x 2 (n_flatten = 1024, "
                     "carla_model.h:110)", -1);
   if (cfg->max_batch <= 0) return ppo_fail("ppo_carla_create: max_batch must be positive", -1);
+  if (pos_enc && (L.conv_oh[0] > kPosMaxOH || L.conv_ow[0] > kPosMaxOW))
+    return ppo_fail("ppo_carla_create3: positional encoding needs a first convolution of at most " +
+                    std::to_string(kPosMaxOH) + " x " + std::to_string(kPosMaxOW) + " outputs", -1);
   if ((long)L.C * L.conv_k[0] * L.conv_k[0] > kMaxKTab || 1280 > kMaxKTab)
     return ppo_fail("ppo_carla_create: too many input channels", -1);
   if (hipSetDevice(device) != hipSuccess) return ppo_fail("ppo_carla_create: hipSetDevice failed", -2);
@@ -316,6 +349,9 @@ extern "C" int ppo_carla_get_layout(const ppo_carla_t* c, ppo_carla_layout* out)
   if (c->any_ln)
     return ppo_fail("ppo_carla_get_layout: ppo_carla_layout cannot describe a LayerNorm agent's tensors; use "
                     "ppo_carla_get_layout2", -1);
+  if (carla_pos(c->L))
+    return ppo_fail("ppo_carla_get_layout: ppo_carla_layout cannot describe a positional agent's cnn.0.weight "
+                    "([8, C + 2, 5, 5]); use ppo_carla_get_layout2", -1);
   // the default arch's layout2 holds ppo_carla_layout's fields with the same values, in the same order
   // up to the tensor table
   const ppo_carla_layout2& L = c->L;
@@ -365,7 +401,14 @@ int carla_forward(const ppo_carla_t* c, CarlaFwdBufs& fb, hipStream_t s, int n, 
                   float* action, float* logprob, float* entropy, float* value, float* alpha, float* beta) {
   const ppo_carla_layout2& L = c->L;
   const float* P = c->P;
+  if (carla_pos(L))  // conv1's row / column tables from its current weights (as k_conv1_wprep's table)
+    (void)launch_pos_bias(L.conv_oc[0], L.conv_ic[0], L.C, L.conv_k[0], L.conv_s[0], L.IH, L.IW, P + L.conv_w[0], fb.posb,
+                          fb.posb + (size_t)L.conv_oc[0] * L.conv_oh[0], s);
   auto conv = [&](ConvArgs a) {
+    if (a.in_u8 && fb.posb) {
+      a.rowb = fb.posb;
+      a.colb = fb.posb + (size_t)L.conv_oc[0] * L.conv_oh[0];
+    }
     a.wprep = fb.c1w;
     a.bx = c->c1bx;
     a.tiled = c->conv_t;
@@ -711,7 +754,7 @@ static size_t carla_part_floats(const ppo_carla_layout2& L, const CarlaNet& net,
     if (f > m) m = f;
   };
   for (int i = 0; i < PPO_CARLA_NCONV; ++i)
-    need(L.conv_oc[i], L.conv_ic[i] * L.conv_k[i] * L.conv_k[i], B * L.conv_oh[i] * L.conv_ow[i]);
+    need(L.conv_oc[i], carla_in_c(L, i) * L.conv_k[i] * L.conv_k[i], B * L.conv_oh[i] * L.conv_ow[i]);
   for (const CarlaLayer& e : net.layer) need(e.OUT, e.IN, B);
   need(L.A, 256, B);  // dist_mu, dist_sigma
   return m;
@@ -755,6 +798,10 @@ static int carla_train_init(ppo_carla_t* c) {
       if (l.F) f = std::max(f, ln_part_floats((int)B, l.F));
     c->lnpart_floats = f;
     rc |= carla_alloc(&c->lnpart, f);
+  }
+  if (carla_pos(L)) {
+    c->pospart_floats = pos_part_floats((int)B, L.conv_oc[0], L.conv_oh[0], L.conv_ow[0]);
+    rc |= carla_alloc(&c->pospart, c->pospart_floats);
   }
   // [0,2) adv mean/std, [64,71) stats + {total, coef}, [128,384) int64 tensor table, [384,...) norm slices
   rc |= carla_alloc(&c->small, kSmallNorm + PPO_CARLA_MAX_TENSORS2 * kNormSplit);
@@ -859,6 +906,10 @@ extern "C" int ppo_carla_update(ppo_carla_t* c, const ppo_carla_train_config* tc
     const float* xf = i > 0 ? c->act[i - 1] : nullptr;
     bad |= launch_wgrad(wgrad_args(L, i, dz, dzs, xf, i ? nullptr : bev, n, c->wgrad_group), G + L.conv_w[i],
                         G + L.conv_b[i], c->part, c->part_floats, s, c->conv_img, c->c1bx, c->wgrad_t);
+    if (i == 0 && carla_pos(L))  // the two coordinate planes' slices of cnn.0.weight's gradient
+      bad |= launch_pos_wgrad(n, L.conv_oc[0], L.conv_oh[0], L.conv_ow[0], L.conv_k[0], L.conv_s[0], L.IH, L.IW, dz, dzs,
+                              G + L.conv_w[0] + (long)L.C * L.conv_k[0] * L.conv_k[0],
+                              (long)L.conv_ic[0] * L.conv_k[0] * L.conv_k[0], c->pospart, c->pospart_floats, s);
     if (i > 0) {
       const DgradArgs da = dgrad_args(L, i, P, dz, dzs, xf, c->dact[i - 1], n);
       if (c->dgrad_col && dgrad_col_layer(L.conv_oh[i], L.conv_ow[i], L.conv_k[i], L.conv_s[i]))

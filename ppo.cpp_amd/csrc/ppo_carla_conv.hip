@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     for (int u = 0; u < NP; ++u) acc[t][u] = f4{0.f, 0.f, 0.f, 0.f};
   const int kbeg = a.kc ? (int)blockIdx.z * a.kc : 0, kend = a.kc ? min(Kt, kbeg + a.kc) : Kt;
   // staging: thread (o = tid >> 2 + 64 h, c = tid & 3) owns channel oc0 + o, k-steps st = c: k0 + 4 c .. + 3
-  const bool vec = (Kt & 3) == 0;  // rows start on 16-byte boundaries (uniform)
+  // conv1 of a positional agent: its filters are wider than the IC image channels read here
+  const int ws = U8 && a.wstride ? a.wstride : Kt;
+  const bool vec = ((Kt | ws) & 3) == 0;  // rows start on 16-byte boundaries (uniform)
   constexpr int NH = (16 * NOT + 63) / 64;
   const int so = tid >> 2, sc = tid & 3;
   f4 wreg[NH];
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     for (int h = 0; h < NH; ++h) {
       const int o = so + 64 * h, oc = oc0 + o, k = k0 + 4 * sc;
       const bool ocok = o < 16 * NOT && oc < a.OC;
-      const float* row = a.W + (long)(ocok ? oc : 0) * Kt;
+      const float* row = a.W + (long)(ocok ? oc : 0) * ws;
       f4 v;
       if (vec) {
         v = *reinterpret_cast<const f4*>(row + min(k, Kt - 4));
@@ -116,9 +118,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         const long off = ok ? xbase[u] + ko : 0;
         if constexpr (U8) {
           // unconditional load, masked as an integer; x / 255 as x * (1 / 255) (within 1 ulp of the
-          // reference's division: a division sequence serialises the gather behind VCC)
+          // reference's division: a division sequence serialises the gather behind VCC); xscale is
+          // 1 for a positional agent, whose reference never divides
           const int raw = a.in_u8[off];
-          x[st][u] = (float)(ok ? raw : 0) * (1.0f / 255.0f);
+          x[st][u] = (float)(ok ? raw : 0) * a.xscale;
         } else {
           x[st][u] = a.in_f[off] * (ok ? 1.0f : 0.0f);  // a multiplicative mask keeps the load unconditional
         }
@@ -156,6 +159,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
   for (int u = 0; u < NP; ++u) {
     if (!qv[u]) continue;
     float* o = a.out + obase[u];
+    int poy = 0, pox = 0;  // conv1 of a positional agent: this pixel's row and column
+    if constexpr (U8) {
+      if (a.rowb) {
+        const long q = q0 + 16 * u + j;
+        const int p = (int)(q - (q / P) * P);
+        poy = p / a.OW;
+        pox = p - poy * a.OW;
+      }
+    }
 #pragma unroll
     for (int t = 0; t < NOT; ++t)
 #pragma unroll
@@ -163,6 +175,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         const int oc = oc0 + 16 * t + 4 * g + r;
         if (oc < a.OC) {
           float y = acc[t][u][r] + a.b[oc];
+          if constexpr (U8) {
+            if (a.rowb) y += a.rowb[oc * a.OH + poy] + a.colb[oc * a.OW + pox];
+          }
           if (a.relu) y = y > 0.0f ? y : 0.0f;
           o[(long)oc * P] = y;
         }
@@ -413,7 +428,7 @@ __global__ __launch_bounds__(256) void k_conv_img(ConvArgs a) {
   }
   for (int e = tid; e < OC * Ktp; e += 256) {
     const int oc = e / Ktp, k = e - oc * Ktp;
-    wl[e] = k < Kt ? a.W[oc * Kt + k] : 0.0f;
+    wl[e] = k < Kt ? a.W[oc * (a.wstride ? a.wstride : Kt) + k] : 0.0f;
   }
   for (int k = tid; k < Kt + 64; k += 256) {
     const int ic = k / KK, rem = k - ic * KK, ky = rem / K, kx = rem - ky * K;
@@ -437,7 +452,7 @@ __global__ __launch_bounds__(256) void k_conv_img(ConvArgs a) {
       const int k = k0 + 4 * st + g;
       const int ko = koff[k];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) x[st][u] = (float)tile[ko + pix[u]] * (1.0f / 255.0f);
+      for (int u = 0; u < 4; ++u) x[st][u] = (float)tile[ko + pix[u]] * a.xscale;
       w[st] = wrow[k] * wm;
     }
 #pragma unroll
@@ -456,6 +471,7 @@ __global__ __launch_bounds__(256) void k_conv_img(ConvArgs a) {
       const int oc = 4 * g + r;
       if (oc < OC) {
         float y = acc[u][r] + a.b[oc];
+        if (a.rowb) y += a.rowb[oc * a.OH + oy] + a.colb[oc * a.OW + ox];
         if (a.relu) y = y > 0.0f ? y : 0.0f;
         o[(size_t)oc * P] = y;
       }
@@ -515,7 +531,11 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a) {
       *reinterpret_cast<unsigned*>(tile + (ic * TI + r) * TIP + 4 * d) = v;
     }
   }
-  for (int e = tid; e < OC * Kt; e += 256) wl[e] = a.W[e];
+  if (a.wstride) {  // a positional agent's wider filters: the image channels of each
+    for (int e = tid; e < OC * Kt; e += 256) wl[e] = a.W[(e / Kt) * a.wstride + e % Kt];
+  } else {
+    for (int e = tid; e < OC * Kt; e += 256) wl[e] = a.W[e];
+  }
   for (int k = tid; k < Kx + 64; k += 256) {
     const int ic = k / (K * KX), rem = k - ic * (K * KX), ky = rem / KX, kxp = rem - ky * KX;
     const bool in = k < Kx;
@@ -543,7 +563,7 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a) {
       const float wv = wrow[(wt >> 8) + min(max(kx, 0), K - 1)];
       w[st] = ok ? wv : 0.0f;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) x[st][u] = (float)tile[po + pix[u]] * (1.0f / 255.0f);
+      for (int u = 0; u < 4; ++u) x[st][u] = (float)tile[po + pix[u]] * a.xscale;
     }
 #pragma unroll
     for (int st = 0; st < UK; ++st)
@@ -561,6 +581,7 @@ __global__ __launch_bounds__(256) void k_conv_img2(ConvArgs a) {
       const int ocp = 4 * g + r, oc = ocp & 7, ox = tx * kImg2W + 2 * j + (ocp >> 3);
       if (oc < OC && ox < a.OW) {
         float y = acc[u][r] + a.b[oc];
+        if (a.rowb) y += a.rowb[oc * a.OH + oy] + a.colb[oc * a.OW + ox];
         if (a.relu) y = y > 0.0f ? y : 0.0f;
         a.out[(size_t)smp * a.out_stride + (size_t)oc * P + (size_t)oy * a.OW + ox] = y;
       }
@@ -593,16 +614,18 @@ static size_t img3_lds_bytes(int IC, int K, int S) {
   return ((size_t)IC * TI * TIP + 15) & ~(size_t)15;
 }
 // wprep[((kb * 4 + g) * 16 + i) * 4 + st] = A[i][tap 16 kb + 4 g + st]
+// wstride: floats between two filters of W (IC K K, or more for a positional agent); xscale: the
+// image's scale (1 / 255, or 1), folded into the weights
 __global__ void k_conv1_wprep(const float* __restrict__ W, float* __restrict__ wp, int IC, int K, int S, int OC,
-                              int nblk) {
+                              int nblk, int wstride, float xscale) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= nblk * 256) return;
   const int st = e & 3, i = (e >> 2) & 15, g = (e >> 6) & 3, kb = e >> 8;
   const int r = 2 * kb + (g >> 1), kxp = 4 * (g & 1) + st;
   const int oc = i & 7, dx = i >> 3, kx = kxp - S * dx;
   float w = 0.0f;
-  if (oc < OC && r < IC * K && kx >= 0 && kx < K) w = W[((size_t)oc * IC * K + r) * K + kx];  // W[oc][ic][ky][kx]
-  wp[e] = w * (1.0f / 255.0f);  // the image's 1 / 255 moves onto the weights: B is the raw byte value
+  if (oc < OC && r < IC * K && kx >= 0 && kx < K) w = W[(size_t)oc * wstride + (size_t)r * K + kx];  // W[oc][ic][ky][kx]
+  wp[e] = w * xscale;  // the image's 1 / 255 moves onto the weights: B is the raw byte value
 }
 
 // A workgroup walks tiles [t0, t1) (sample-major, 18 per 192 x 192 sample) with the A-operand table
@@ -741,6 +764,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_img3(ConvArgs a, int tiles, int
         const int ocp = 4 * g + r, oc = ocp & 7, ox = tx * kImg2W + 2 * j + (ocp >> 3);
         if (oc < a.OC && ox < a.OW) {
           float y = acc[u][r] + a.b[oc];
+          if (a.rowb) y += a.rowb[oc * a.OH + oy] + a.colb[oc * a.OW + ox];
           if (a.relu) y = y > 0.0f ? y : 0.0f;
           a.out[(size_t)smp * a.out_stride + (size_t)oc * P + (size_t)oy * a.OW + ox] = y;
         }
@@ -759,7 +783,7 @@ int launch_conv(const ConvArgs& a, hipStream_t s, int img, bool fin, int* z_out)
       img3_patch_bytes(a.IC, a.K, a.S) + (size_t)img3_blocks(a.IC, a.K) * 1024 <= 80 * 1024) {
     const int nblk = img3_blocks(a.IC, a.K);
     hipLaunchKernelGGL(k_conv1_wprep, dim3((nblk * 256 + 255) / 256), dim3(256), 0, s, a.W, a.wprep, a.IC, a.K, a.S,
-                       a.OC, nblk);
+                       a.OC, nblk, a.wstride ? a.wstride : a.IC * a.K * a.K, a.xscale);
     const int tiles = ((a.OW + kImg2W - 1) / kImg2W) * ((a.OH + kImgTile - 1) / kImgTile) * a.n;
     const int grid = std::min(tiles, kImg3WG), tpc = (tiles + grid - 1) / grid;
     const size_t lds = img3_patch_bytes(a.IC, a.K, a.S) + (size_t)nblk * 256 * sizeof(float);

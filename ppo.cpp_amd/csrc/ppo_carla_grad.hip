@@ -641,7 +641,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
           const bool ok = qv && kc[u] == 0;
           const long off = ok ? xb + ko[u] : 0;
           const int raw = a.x_u8[off];
-          const float v = (float)(ok ? raw : 0) * (1.0f / 255.0f);
+          const float v = (float)(ok ? raw : 0) * a.xscale;
           bv[st][u] = (qv && kc[u] == 1) ? 1.0f : v;
         }
       } else {
@@ -770,7 +770,7 @@ __global__ __launch_bounds__(256) void k_wgrad_img(WgradArgs a, int tiles_x, int
 #pragma unroll
       for (int u = 0; u < kWimgCT; ++u) {
         const int raw = tile[ko[u] + po];
-        const float xv = (float)raw * (1.0f / 255.0f);
+        const float xv = (float)raw * a.xscale;
         // columns >= Kt (bias, padding) exist only in the last tile of the last wave
         const float bv = u == kWimgCT - 1 ? (cb[u] < 0.0f ? xv : cb[u]) : xv;
         acc[u] = mfma16(av, bv, acc[u]);
@@ -799,7 +799,8 @@ __global__ __launch_bounds__(256) void k_wgrad_img(WgradArgs a, int tiles_x, int
 // 25 % fewer MFMAs than k_wgrad_img; the pixel sum is split into its even and odd halves, so the
 // result differs from k_wgrad's in rounding only. The combine runs once per workgroup through LDS.
 // The B operands are the raw byte values (exact in fp32) and the workgroup's tap sums are scaled by
-// 1 / 255 once in the combine (round 5: one VALU fewer per MFMA; the bias column is not scaled).
+// the image's scale (WgradArgs::xscale: 1 / 255, or 1 for a positional agent) once in the combine
+// (round 5: one VALU fewer per MFMA; the bias column is not scaled).
 constexpr int kWimg2CT = 9;  // column tiles per wave: 4 x 9 x 16 = 576 >= IC K (K + S) + 1 = 526
 static size_t wimg2_lds_bytes(int IC, int K, int S, int OC) {
   const int TI = (kImgTile - 1) * S + K, TIP = (TI + 3) & ~3;
@@ -923,7 +924,7 @@ __global__ __launch_bounds__(256, 3) void k_wgrad_img2(WgradArgs a, int tiles_x,
 #pragma unroll
       for (int u = 0; u < kWimg2CT; ++u) {
         const int raw = tile[ko[u] + po];
-        const float xv = (float)raw;  // the image's 1 / 255 is applied once, in the combine below
+        const float xv = (float)raw;  // the image's scale is applied once, in the combine below
         // the bias and padding columns lie in the last 4 tiles of the last wave (launch condition)
         const float bv = u >= kWimg2CT - 4 ? (cb[u] < 0.0f ? xv : cb[u]) : xv;
         acc[u] = mfma16(av, bv, acc[u]);
@@ -949,7 +950,7 @@ __global__ __launch_bounds__(256, 3) void k_wgrad_img2(WgradArgs a, int tiles_x,
     } else {
       const int ic = k / (K * K), rem = k - ic * (K * K), ky = rem / K, kx = rem - ky * K;
       const int c = (ic * K + ky) * KX + kx;
-      v = (dl[oc * NC + c] + dl[(oc + 8) * NC + c + S]) * (1.0f / 255.0f);
+      v = (dl[oc * NC + c] + dl[(oc + 8) * NC + c + S]) * a.xscale;
     }
     out[e] = v;
   }
@@ -1197,7 +1198,8 @@ __global__ __launch_bounds__(256, 4) void k_wgrad_t2(WgradArgs a, int tiles_x, i
   }
 }
 
-// G[w + oc*Kt + k] / G[b + oc] = sum over chunks. Level 1 (k_wsum1) adds groups of kSumGroup
+// G[w + oc*wstride + k] / G[b + oc] = sum over chunks (wstride = Kt, or more where the filters hold
+// channels the gathered columns do not cover: a positional agent's conv1). Level 1 (k_wsum1) adds groups of kSumGroup
 // consecutive chunks in parallel (blockIdx.y = group), level 2 (k_wsum) adds the group sums in order:
 // a fixed order, so the result is deterministic.
 constexpr int kSumGroup = 32;
@@ -1211,15 +1213,15 @@ __global__ void k_wsum1(const float* __restrict__ part, int chunks, long per, fl
   out[(long)blockIdx.y * per + i] = acc;
 }
 
-__global__ void k_wsum(const float* __restrict__ part, int chunks, int OC, int Kt, float* __restrict__ Gw,
-                       float* __restrict__ Gb, int accum) {
+__global__ void k_wsum(const float* __restrict__ part, int chunks, int OC, int Kt, int wstride,
+                       float* __restrict__ Gw, float* __restrict__ Gb, int accum) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per = (long)OC * (Kt + 1);
   if (i >= per) return;
   float acc = 0.f;
   for (int c = 0; c < chunks; ++c) acc += part[(long)c * per + i];
   const int oc = (int)(i / (Kt + 1)), k = (int)(i - (long)oc * (Kt + 1));
-  float* o = k < Kt ? Gw + (long)oc * Kt + k : Gb + oc;
+  float* o = k < Kt ? Gw + (long)oc * wstride + k : Gb + oc;
   *o = accum ? *o + acc : acc;  // accum: a later sample group of launch_wgrad's split
 }
 
@@ -1322,13 +1324,14 @@ WgradPlan plan_wgrad(int OC, int Kt, long Q) {
 static void launch_wsum(const WgradArgs& a, int chunks, float* Gw, float* Gb, int accum, hipStream_t s) {
   const long per = (long)a.OC * (a.Kt + 1);
   const unsigned gb = (unsigned)((per + 255) / 256);
+  const int ws = a.wstride ? a.wstride : a.Kt;
   if (chunks > kSumGroup) {
     const int groups = (chunks + kSumGroup - 1) / kSumGroup;
     float* lvl = a.part + (size_t)chunks * per;
     hipLaunchKernelGGL(k_wsum1, dim3(gb, groups), dim3(256), 0, s, a.part, chunks, per, lvl);
-    hipLaunchKernelGGL(k_wsum, dim3(gb), dim3(256), 0, s, lvl, groups, a.OC, a.Kt, Gw, Gb, accum);
+    hipLaunchKernelGGL(k_wsum, dim3(gb), dim3(256), 0, s, lvl, groups, a.OC, a.Kt, ws, Gw, Gb, accum);
   } else {
-    hipLaunchKernelGGL(k_wsum, dim3(gb), dim3(256), 0, s, a.part, chunks, a.OC, a.Kt, Gw, Gb, accum);
+    hipLaunchKernelGGL(k_wsum, dim3(gb), dim3(256), 0, s, a.part, chunks, a.OC, a.Kt, ws, Gw, Gb, accum);
   }
 }
 

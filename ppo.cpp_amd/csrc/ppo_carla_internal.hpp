@@ -4,8 +4,9 @@
 //   ppo_carla_tail.hip     k_carla_pack, k_carla_head, k_carla_tail and their launchers
 //   ppo_carla_ln.hip       LayerNorm kernels and launchers, the ppo_carla_debug_ln_* hooks
 //   ppo_carla_grad.hip     input- and weight-gradient kernels and launchers
+//   ppo_carla_pos.hip      use_positional_encoding: conv1's row / column tables, the two planes' weight gradient
 //   ppo_carla_rollout.hip  rollout storage, GAE, the epoch loop, act lanes
-// (ppo_carla_units.hpp: what crosses the first five). The rollout object computes through
+// (ppo_carla_units.hpp: what crosses the first six). The rollout object computes through
 // ppo_carla_forward / ppo_carla_update and, for its act lanes, carla_forward on a lane's own buffer set;
 // the rest reads the agent's placement and moves the statistics that every ppo_carla_update leaves on the
 // device, so the epoch loop needs no host synchronisation per minibatch.
@@ -37,6 +38,9 @@ struct CarlaFwdBufs {
   float* ksplit = nullptr;  // split-K partials of the forward's narrow layers (conv_split_z)
   // k_conv_img3's A-operand table: k_conv1_wprep rewrites it from conv1's weights in every forward
   float* c1w = nullptr;
+  // positional agents (ppo_carla_create3): conv1's row / column tables [8][OH] | [8][OW], which
+  // launch_pos_bias rewrites from conv1's weights in every forward, as c1w is
+  float* posb = nullptr;
   unsigned* tail_bar = nullptr;  // k_carla_tail's grid barrier counter
   unsigned tail_count = 0;       // arrivals so far (the counter's value between launches)
   // LayerNorm agents (ppo_carla_create2): per normalised layer the pre-activation z [B][F] and the

@@ -32,6 +32,15 @@ struct ConvArgs {
   float* wprep = nullptr;  // conv1 packed form (k_conv_img3): its A operands, [kImg3Blocks][4][16][4]
   int bx = 0;              // conv1 packed form: 1 runs its products as split-bf16 MFMAs (k_conv_img3<.., BX>)
   int tiled = 0;           // 1: conv2's shape runs k_conv_t (LDS-staged input patches)
+  // uint8 input only (conv1). wstride: floats between two filters of W (0: IC * K * K; a positional
+  // agent's cnn.0.weight is [OC][IC + 2][K][K], of which the image channels are the first IC * K * K).
+  // xscale: what a byte is multiplied by (1 / 255; 1 for a positional agent, carla_model.h:222-236).
+  // rowb [OC][OH] / colb [OC][OW]: the two coordinate planes' part of the pre-activation
+  // (launch_pos_bias), added with the bias; null: none.
+  int wstride = 0;
+  float xscale = 1.0f / 255.0f;
+  const float* rowb = nullptr;
+  const float* colb = nullptr;
 };
 
 constexpr int kMaxKTab = 2048;  // im2col offset table entries (IC * K * K <= 1280 here)
@@ -90,6 +99,8 @@ struct WgradArgs {
   long qchunk;   // output pixels per chunk (multiple of 4)
   float* part;   // [chunks][OC][Kt + 1]
   long group_bytes = 0;  // host only: launch_wgrad_generic's sample-group limit (0: kWgradFar)
+  int wstride = 0;       // floats between two filters of Gw (0: Kt), as ConvArgs::wstride
+  float xscale = 1.0f / 255.0f;  // uint8 input: what a byte is multiplied by, as ConvArgs::xscale
 };
 
 struct WgradPlan {
@@ -124,6 +135,17 @@ __host__ __device__ inline int img3_blocks(int IC, int K) { return (((IC * K + 1
 
 // conv6 only: for conv5 (stride 2, 10 x 10 -> 4 x 4) the col2im pass costs more than the GEMM saves
 // (GEMM 77 + col2im 127 us vs k_dgrad's 182 us; conv6: 5 + 71 + 33 vs 370 us; profiles/r05/carla_tiled/)
+// torch.linspace(-1, 1, n)[i] in fp32, bit for bit (ATen's RangeFactories: step = (end - start) / (n - 1),
+// the first half counts up from the start and the rest down from the end, each one fused multiply-add)
+__host__ __device__ inline float pos_lin(int i, int n) {
+  if (n <= 1) return -1.0f;
+  const float step = (1.0f - (-1.0f)) / (float)(n - 1);
+  return i < n / 2 ? fmaf(step, (float)i, -1.0f) : fmaf(-step, (float)(n - 1 - i), 1.0f);
+}
+constexpr int kPosMaxOW = 256;  // k_pos_rq keeps a lane's column sums in four registers (64 lanes x 4)
+constexpr int kPosMaxOH = 1024; // and a workgroup's row sums in LDS
+constexpr int kPosSPC = 4;      // samples per workgroup of k_pos_rq: its partial count depends on n only
+
 inline bool dgrad_col_layer(int OH, int OW, int K = 3, int S = 1) { return OH * OW <= 16 && K == 3 && S == 1; }
 
 }  // namespace
@@ -151,4 +173,13 @@ int launch_dgrad_col(const DgradArgs& a, float* wt, const float* zbias, float* d
 WgradPlan plan_wgrad(int OC, int Kt, long Q);
 int launch_wgrad(WgradArgs a, float* Gw, float* Gb, float* part, size_t part_cap, hipStream_t s, bool img = true,
                  bool bx = false, bool tiled = false);
+// ppo_carla_pos.hip: use_positional_encoding's two constant input planes, never materialised.
+// rowb [OC][OH], colb [OC][OW] from W [OC][IC_total][K][K] (planes C and C + 1)
+int launch_pos_bias(int OC, int IC_total, int C, int K, int S, int IH, int IW, const float* W, float* rowb,
+                    float* colb, hipStream_t s);
+// floats of the row / column partial sums for up to max_n samples
+size_t pos_part_floats(int max_n, int OC, int OH, int OW);
+// dw [oc * dw_stride + {0, 1} * K * K + ky * K + kx] from dz [n][OC][OH][OW] (sample stride dz_stride)
+int launch_pos_wgrad(int n, int OC, int OH, int OW, int K, int S, int IH, int IW, const float* dz, long dz_stride,
+                     float* dw, long dw_stride, float* part, size_t part_cap, hipStream_t s);
 #pragma GCC visibility pop

@@ -181,10 +181,17 @@ extern "C" int ppo_carla_layout_fill(ppo_carla_layout* L, int C, int IH, int IW,
 
 extern "C" int ppo_carla_layout2_fill(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
                                       const ppo_carla_arch* arch) {
+  return ppo_carla_layout2_fill_pos(L, C, IH, IW, NM, NV, A, arch, 0);
+}
+
+extern "C" int ppo_carla_layout2_fill_pos(ppo_carla_layout2* L, int C, int IH, int IW, int NM, int NV, int A,
+                                          const ppo_carla_arch* arch, int pos_enc) {
   if (!L) return ppo_fail("ppo_carla_layout2_fill: null argument", -1);
+  if (pos_enc != 0 && pos_enc != 1)
+    return ppo_fail("ppo_carla_layout2_fill_pos: pos_enc must be 0 or 1 (use_positional_encoding)", -1);
   if (arch && (arch->encoder_ln < 0 || arch->encoder_ln > 1))
     return ppo_fail("ppo_carla_layout2_fill: encoder_ln must be 0 (roach) or 1 (roach_ln); roach_ln2 is not built", -1);
-  const int rc = ppo_carla_layout2_init(L, C, IH, IW, NM, NV, A, arch);
+  const int rc = ppo_carla_layout2_init_pos(L, C, IH, IW, NM, NV, A, arch, pos_enc);
   if (rc == -2)
     return ppo_fail("ppo_carla_layout2_fill: the roach_ln encoder needs a 192 x 192 bev: the reference hard-codes its "
                     "LayerNorm shapes (carla_model.h:45-62)", -1);

@@ -787,7 +787,15 @@ inline std::vector<float> load_module(const std::string& path, const Spec& spec)
     }
     const Value* v = o->find(rest);
     if (!v || v->kind != Value::TENSOR) throw std::runtime_error("pth: " + path + " has no parameter " + t.name);
-    if (v->shape != t.shape) throw std::runtime_error("pth: shape mismatch for " + t.name + " in " + path);
+    if (v->shape != t.shape) {
+      auto dims = [](const std::vector<int64_t>& sh) {
+        std::string o = "[";
+        for (size_t i = 0; i < sh.size(); ++i) o += (i ? ", " : "") + std::to_string(sh[i]);
+        return o + "]";
+      };
+      throw std::runtime_error("pth: shape mismatch for " + t.name + " in " + path + ": the archive holds " +
+                               dims(v->shape) + ", the module expects " + dims(t.shape));
+    }
     const auto f = v->floats();
     std::copy(f.begin(), f.end(), flat.begin() + t.off);
   }

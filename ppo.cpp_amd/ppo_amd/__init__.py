@@ -265,6 +265,11 @@ SYMBOLS = [
     ("ppo_carla_tensor_name", _I, [C.POINTER(CarlaLayout2), _I, C.c_char_p, _I]),
     ("ppo_carla_pth_save2", _I, [C.POINTER(CarlaLayout2), _FP, C.c_char_p]),
     ("ppo_carla_pth_load2", _I, [C.POINTER(CarlaLayout2), C.c_char_p, _FP, _L]),
+    ("ppo_carla_create3", _I, [C.POINTER(CarlaConfig), C.POINTER(CarlaArch), _I, _I, C.c_char_p, C.POINTER(_VP)]),
+    ("ppo_carla_layout2_fill_pos", _I, [C.POINTER(CarlaLayout2), _I, _I, _I, _I, _I, _I, C.POINTER(CarlaArch), _I]),
+    ("ppo_carla_debug_pos_grid", _I, [_I, _FP]),
+    ("ppo_carla_debug_pos_bias", _I, [_I, _I, _I, _I, _I, _I, _I, _FP, _FP, _FP, _VP]),
+    ("ppo_carla_debug_pos_wgrad", _I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _FP, _FP, _VP]),
     ("ppo_carla_debug_ln_forward", _I, [_I, _I, _FP, _L, _FP, _FP, _FP, _L, _FP, _VP]),
     ("ppo_carla_debug_ln_backward", _I, [_I, _I, _FP, _L, _FP, _FP, _FP, _L, _FP, _FP, _FP, _FP, _VP]),
     ("ppo_carla_comm_allreduce", _I, [_VP, _FP, _L, _I]),
@@ -351,10 +356,14 @@ def carla_arch(encoder="roach", layer_norm=False, policy_layer_norm=True) -> Car
 
 
 def carla_layout2(C_=15, IH=192, IW=192, NM=8, NV=3, A=2, encoder="roach", layer_norm=False,
-                  policy_layer_norm=True) -> CarlaLayout2:
+                  policy_layer_norm=True, positional_encoding=False) -> CarlaLayout2:
+    """positional_encoding (use_positional_encoding): cnn.0.weight is [8, C_ + 2, 5, 5], conv_ic[0] == C_ + 2"""
     L = CarlaLayout2()
     arch = carla_arch(encoder, layer_norm, policy_layer_norm)
-    check(lib().ppo_carla_layout2_fill(C.byref(L), C_, IH, IW, NM, NV, A, C.byref(arch)))
+    if positional_encoding:
+        check(lib().ppo_carla_layout2_fill_pos(C.byref(L), C_, IH, IW, NM, NV, A, C.byref(arch), 1))
+    else:
+        check(lib().ppo_carla_layout2_fill(C.byref(L), C_, IH, IW, NM, NV, A, C.byref(arch)))
     return L
 
 
@@ -817,22 +826,27 @@ class CarlaAgent:
 
     def __init__(self, max_batch, obs_channels=15, bev=192, num_measurements=8, num_value_measurements=3,
                  action_dim=2, beta_min=1.0, seed=1, rank=0, device=0, options: str | None = None,
-                 encoder="roach", layer_norm=False, policy_layer_norm=True):
+                 encoder="roach", layer_norm=False, policy_layer_norm=True, positional_encoding=False):
         """encoder "roach" | "roach_ln", layer_norm (use_layer_norm), policy_layer_norm
-        (use_layer_norm_policy_head): carla_model.h:44-64, :113-175. The default agent's `layout` is a
-        CarlaLayout, a LayerNorm agent's a CarlaLayout2; `layout2` is a CarlaLayout2 for both."""
+        (use_layer_norm_policy_head): carla_model.h:44-64, :113-175. positional_encoding
+        (use_positional_encoding, :38-42, :222-236): cnn.0 takes obs_channels + 2 channels and the bev is
+        NOT divided by 255, as in the reference (include/ppo_carla.h). The default agent's `layout` is a
+        CarlaLayout, a LayerNorm or positional agent's a CarlaLayout2; `layout2` is a CarlaLayout2 for all."""
         self.cfg = CarlaConfig(obs_channels, bev, bev, num_measurements, num_value_measurements, action_dim, beta_min,
                                max_batch, seed, rank)
         self._h = C.c_void_p()
         self.arch = carla_arch(encoder, layer_norm, policy_layer_norm)
         opts = options.encode() if options else None
-        if self.arch.encoder_ln or self.arch.mlp_ln:
+        self.positional_encoding = bool(positional_encoding)
+        if self.positional_encoding:
+            check(lib().ppo_carla_create3(C.byref(self.cfg), C.byref(self.arch), 1, device, opts, C.byref(self._h)))
+        elif self.arch.encoder_ln or self.arch.mlp_ln:
             check(lib().ppo_carla_create2(C.byref(self.cfg), C.byref(self.arch), device, opts, C.byref(self._h)))
         else:
             check(lib().ppo_carla_create_ex(C.byref(self.cfg), device, opts, C.byref(self._h)))
         self.layout2 = CarlaLayout2()
         check(lib().ppo_carla_get_layout2(self._h, C.byref(self.layout2)))
-        if self.arch.encoder_ln or self.arch.mlp_ln:
+        if self.arch.encoder_ln or self.arch.mlp_ln or self.positional_encoding:
             self.layout = self.layout2
         else:
             self.layout = CarlaLayout()
@@ -1144,6 +1158,31 @@ def carla_gather_f32(srcs, idx: "DeviceArray", dsts, n, widths):
     dp = (C.c_void_p * k)(*[d.ptr for d in dsts])
     w = (C.c_int * k)(*widths)
     check(lib().ppo_carla_debug_gather_f32(n, k, sp, w, idx.ptr, dp, None))
+
+
+def carla_pos_grid(n) -> np.ndarray:
+    """ppo_carla_debug_pos_grid: the library's torch.linspace(-1, 1, n) in fp32 (host only)"""
+    out = np.empty(n, np.float32)
+    check(lib().ppo_carla_debug_pos_grid(int(n), out.ctypes.data))
+    return out
+
+
+def carla_pos_bias(W: "DeviceArray", OC, IC_total, C_, K, S, IH, IW):
+    """ppo_carla_debug_pos_bias: (rowb [OC, OH], colb [OC, OW]) of W [OC, IC_total, K, K]'s planes C_, C_ + 1"""
+    OH, OW = (IH - K) // S + 1, (IW - K) // S + 1
+    rowb, colb = DeviceArray((OC, OH), np.float32), DeviceArray((OC, OW), np.float32)
+    check(lib().ppo_carla_debug_pos_bias(OC, IC_total, C_, K, S, IH, IW, W.ptr, rowb.ptr, colb.ptr, None))
+    return rowb, colb
+
+
+def carla_pos_wgrad(dz: "DeviceArray", n, OC, K, S, IH, IW, max_n=None):
+    """ppo_carla_debug_pos_wgrad: dW [OC, 2, K, K] of the two coordinate planes from dz [n, OC, OH, OW],
+    with partial-sum buffers sized for max_n rows"""
+    OH, OW = (IH - K) // S + 1, (IW - K) // S + 1
+    dw = DeviceArray((OC, 2, K, K), np.float32)
+    check(lib().ppo_carla_debug_pos_wgrad(n, n if max_n is None else max_n, OC, OH, OW, K, S, IH, IW, dz.ptr, dw.ptr,
+                                          None))
+    return dw
 
 
 def carla_ln_forward(z: "DeviceArray", gamma: "DeviceArray", beta: "DeviceArray", n, F, in_stride=None,

@@ -5,7 +5,8 @@ ppo_carla_forward with inputs resident in HBM, and the algorithmic MFMA rate (87
 SURVEY §8d), and of the PPO minibatch update (ppo_carla_update, counted as 3x the forward:
 forward + two backward GEMMs per layer). --encoder roach_ln / --layer-norm time the LayerNorm variants
 (ppo_carla_create2); their parameters come from tests/carla_ln_ref.py's init_params (LayerNorm weights
-U(0.5, 1.5)), as the default agent's come from tests/carla_inputs.py."""
+U(0.5, 1.5)), as the default agent's come from tests/carla_inputs.py. --positional-encoding times
+use_positional_encoding (ppo_carla_create3) on the same parameter distributions over the wider cnn.0.weight."""
 import argparse
 import json
 import os
@@ -31,10 +32,13 @@ def main():
     ap.add_argument("--options", default="", help="ppo_carla_create_ex options, e.g. tail=layers")
     ap.add_argument("--encoder", default="roach", choices=["roach", "roach_ln"], help="image_encoder")
     ap.add_argument("--layer-norm", action="store_true", help="use_layer_norm (with the policy head's)")
+    ap.add_argument("--positional-encoding", action="store_true", help="use_positional_encoding")
     args = ap.parse_args()
     ppo_amd.set_device(0)
     arch = dict(encoder=args.encoder, layer_norm=args.layer_norm)
-    if args.encoder == "roach" and not args.layer_norm:
+    if args.positional_encoding:
+        arch["positional_encoding"] = True
+    if args.encoder == "roach" and not args.layer_norm and not args.positional_encoding:
         L = CI.layout()
         p = CI.params(L)
     else:
