@@ -9,6 +9,14 @@
  * bit for bit, to the host SyntheticCheetah in ppo.cpp_amd/gymcpp/synthetic/ and oracle/):
  *   q'_i = fma(0.9, q_i, fma(0.1, a_{i mod A}, 0.05 * q_{(i+1) mod O}))
  *   r    = (q'_0 - q_0) / 0.05 - sum_k (0.1 a_k) a_k ;  truncation after 1000 steps, never terminates
+ *
+ * A second env kind, PSYN_PENDULUM (psyn_create_env("Pendulum-v1")), is a real task: Gymnasium's
+ * Pendulum-v1 (O = 3, A = 1, torque in [-2, 2], truncation after 200 steps, never terminates), with
+ * the arithmetic of include/ppo_pendulum.h — bit for bit the host env ppo.cpp_amd/gymcpp/pendulum.h.
+ * The vector-env semantics, the episode statistics and the wrapper chain are the same for both kinds.
+ * Its state q [E, 3] holds theta, thetadot and one unused slot. The dynamics clip the torque to
+ * [-2, 2] themselves, whatever psyn_set_action_space says. Not covered for this kind: the VALU
+ * rollout kernel (rollout_kernel=valu is refused).
  */
 #ifndef PPO_SYNTH_ENV_H
 #define PPO_SYNTH_ENV_H
@@ -20,6 +28,14 @@ extern "C" {
 typedef struct psyn_env psyn_t;
 
 int psyn_create(int num_envs, int obs_dim, int act_dim, psyn_t** out);
+/* The env kinds. psyn_create gives PSYN_CHEETAH at any (obs_dim, act_dim). */
+enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1 };
+/* By env id: "Pendulum-v1" (PSYN_PENDULUM: O = 3, A = 1, action space [-2, 2]) or
+ * "SyntheticCheetah-v0" (the env of psyn_create(num_envs, 17, 6)). Any other id, a NULL argument or
+ * num_envs <= 0 is refused (-1, ppo_last_error lists the ids) before any HIP call. */
+int psyn_create_env(const char* env_id, int num_envs, psyn_t** out);
+/* kind, dims and the truncation step count (1000 | 200); any output may be NULL */
+int psyn_env_info(const psyn_t* env, int* kind, int* obs_dim, int* act_dim, int* max_steps);
 int psyn_destroy(psyn_t* env);
 /* reset(seed + i) for every env; writes obs [E,O] and done [E] (= 0) */
 int psyn_reset(psyn_t* env, int seed, float* obs_dev, float* done_dev, void* stream);

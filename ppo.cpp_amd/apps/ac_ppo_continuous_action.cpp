@@ -231,7 +231,7 @@ int main(int argc, const char** argv) {
     EnvShape sh;
     if (!device_env_shape(config.env_id, &sh)) {
       std::cerr << "env_backend device: unknown env_id " << config.env_id
-                << " (HalfCheetah-v5, Humanoid-v4, Ant-v5, Hopper-v5, SyntheticCheetah-v0)\n";
+                << " (" << device_env_ids() << ")\n";
       return 1;
     }
     O = sh.O; A = sh.A; act_lo = sh.lo; act_hi = sh.hi;
@@ -333,7 +333,7 @@ int main(int argc, const char** argv) {
     std::vector<float> obs_mean_std;       // env 0's observations (ac:663, estimate_mean_std)
     std::vector<hipStream_t> gstreams(G);
     if (device_env) {
-      check(psyn_create(E, O, A, &denv), "psyn_create");
+      check(create_device_env(config.env_id, E, EnvShape{O, A, act_lo, act_hi}, &denv), "psyn_create");
       check(psyn_set_action_space(denv, act_lo, act_hi), "psyn_set_action_space");
       check(psyn_reset(denv, config.seed, d_obs, d_done, s), "psyn_reset");  // env i: seed + i on every rank (ac:606)
     } else {

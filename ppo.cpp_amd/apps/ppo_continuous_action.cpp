@@ -112,7 +112,7 @@ int main(int argc, const char** argv) {
   if (device_env) {
     if (!device_env_shape(config.env_id, &sh)) {
       std::cerr << "env_backend device: unknown env_id " << config.env_id
-                << " (HalfCheetah-v5, Humanoid-v4, Ant-v5, Hopper-v5, SyntheticCheetah-v0)\n";
+                << " (" << device_env_ids() << ")\n";
       return 1;
     }
   } else {
@@ -159,7 +159,7 @@ int main(int argc, const char** argv) {
     hipStream_t s = (hipStream_t)ppo_stream(agent);
 
     if (device_env) {  // ParVectorEnv(make_env(...)) on the device: synthetic env + the ppo:41-49 chain
-      check(psyn_create(E, O, A, &denv), "psyn_create");
+      check(create_device_env(config.env_id, E, sh, &denv), "psyn_create");
       if (config.clip_actions) check(psyn_set_action_space(denv, sh.lo, sh.hi), "psyn_set_action_space");
       else check(psyn_set_action_space(denv, -3.0e38f, 3.0e38f), "psyn_set_action_space");
       check(pwrap_create(E, O, config.gamma, &dwrap), "pwrap_create");

@@ -26,6 +26,7 @@
 #include "../../include/ppo_synth_env.h"
 #include "../../include/ppo_env_wrappers.h"
 #include "ppo_kernels.hpp"
+#include "../../include/ppo_pendulum.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -1681,6 +1682,34 @@ extern "C" int psyn_create(int E, int O, int A, psyn_t** out) {
   return 0;
 }
 
+// every check comes before the first HIP call (psyn_create's hipGetDevice)
+extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
+  if (!env_id || !out) return fail("psyn_create_env: null argument");
+  if (E <= 0) return fail("psyn_create_env: num_envs must be positive");
+  const std::string id = env_id;
+  if (id == "SyntheticCheetah-v0") return psyn_create(E, 17, 6, out);
+  if (id != "Pendulum-v1")
+    return fail("psyn_create_env: unknown env_id " + id + " (Pendulum-v1, SyntheticCheetah-v0)");
+  if (int rc = psyn_create(E, PEND_OBS_DIM, PEND_ACT_DIM, out)) return rc;
+  (*out)->a.kind = PSYN_PENDULUM;
+  (*out)->act_lo = -PEND_MAX_TORQUE;
+  (*out)->act_hi = PEND_MAX_TORQUE;
+  // the unused third state slot is defined from the start (the persistent kernels carry it along)
+  HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * PEND_OBS_DIM));
+  return 0;
+}
+
+static int psyn_max_steps(const psyn_t* env) { return env->a.kind == PSYN_PENDULUM ? PEND_MAX_STEPS : 1000; }
+
+extern "C" int psyn_env_info(const psyn_t* env, int* kind, int* obs_dim, int* act_dim, int* max_steps) {
+  if (!env) return fail("psyn_env_info: null env");
+  if (kind) *kind = env->a.kind;
+  if (obs_dim) *obs_dim = env->a.O;
+  if (act_dim) *act_dim = env->a.A;
+  if (max_steps) *max_steps = psyn_max_steps(env);
+  return 0;
+}
+
 extern "C" int psyn_destroy(psyn_t* env) {
   if (!env) return 0;
   SynthArgs& a = env->a;
@@ -1752,7 +1781,9 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
     {
       ProfScope ps(c, PK_ROLLOUT, c->stream);
       if (const int lrc = launch_rollout(r, c->stream))
-        return fail(lrc == -3 ? "ppo_rollout_synth: rollout_kernel=valu needs the LayerNorm-Beta agent, O <= 32 and no "
+        return fail(lrc == -4 ? "ppo_rollout_synth: rollout_kernel=valu steps the synthetic cheetah only; this env's "
+                                "kind is PSYN_PENDULUM (Pendulum-v1): use rollout_kernel=auto or mfma"
+                    : lrc == -3 ? "ppo_rollout_synth: rollout_kernel=valu needs the LayerNorm-Beta agent, O <= 32 and no "
                                 "device env wrappers"
                               : "ppo_rollout_synth: rollout kernel launch failed");
       if (r.s_beta) launch_beta_logp(r.s_beta, c->buf[PPO_BUF_LOGPROBS], (long)E * c->cfg.num_steps, c->K.A, c->stream);
@@ -1799,9 +1830,10 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
   if (cfg->chunk_steps < 0 || (cfg->mode != 0 && cfg->mode != 1)) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
   const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : 4096;
   const bool persistent = cfg->mode == 0 && eval_supported(c->K) == 0 && !env->a.w.on;
-  // the synthetic env truncates after 1000 steps and resets on the next one: an env finishes at most
-  // one episode per 1001 steps, which bounds the events of a chunk (an overflow is still detected)
-  const long devcap = (long)nE * (chunk / 1001 + 2);
+  // the env truncates after max_steps (1000; Pendulum 200) steps and resets on the next one: an env
+  // finishes at most one episode per max_steps + 1 steps, which bounds the events of a chunk (an
+  // overflow is still detected)
+  const long devcap = (long)nE * (chunk / (psyn_max_steps(env) + 1) + 2);
   hipStream_t s = c->stream;
   struct Scratch {
     char* p = nullptr;

@@ -12,9 +12,12 @@
 // Events go to a global buffer through a vector atomic counter, in any order; the host sorts them by
 // (step, env) (ppo_eval_events.hpp).
 #include "ppo_rollout_common.hpp"
+#include "ppo_pendulum_dev.hpp"
 
-template <int NTO, int NHT>
+// KIND: the device env's kind, compile-time as in k_rollout
+template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
+  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1");
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -112,8 +115,51 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
       ACT[r * 24 + ai] = (s01 - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
     }
     lds_barrier();
-    // ---- env step (k_synth_step arithmetic): 32 lanes per env; a finished episode is one event ----
-    {
+    // ---- env step: 32 lanes per env; a finished episode is one event ----
+    if constexpr (KIND == PSYN_PENDULUM) {
+      // Pendulum-v1 (k_pend_step arithmetic): lane 0 of each env's lane group steps the env
+#pragma clang fp contract(off)
+      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float th, thd, o3[PEND_OBS_DIM];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          pend_reset_dev(rc, rs, &th, &thd);
+          pend_obs(th, thd, o3);
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EVI[EV_AR * R + r] = 0;
+        } else {
+          th = q[0];
+          thd = q[1];
+          const float rw = pend_step(&th, &thd, fminf(fmaxf(ACT[r * 24], a.lo), a.hi), o3);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool tr = tt >= PEND_MAX_STEPS;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (tr) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+            const unsigned slot = atomicAdd(a.count, 1u);
+            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
+          }
+          EVI[EV_AR * R + r] = tr ? 1 : 0;
+        }
+        q[0] = th;
+        q[1] = thd;
+#pragma unroll
+        for (int i = 0; i < PEND_OBS_DIM; ++i) xo[i] = o3[i];
+      }
+    } else {
+      // the synthetic cheetah (k_synth_step arithmetic)
 #pragma clang fp contract(off)
       const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
       const bool live = e < E;
@@ -231,19 +277,21 @@ int eval_supported(const PackedLayout& K) {
   return (K.kind == PPO_NET_LN_BETA && K.H == 256 && 2 * K.A <= 16 && (K.OP == 16 || K.OP == 32)) ? 0 : -1;
 }
 
-template <int NTO>
+template <int NTO, int KIND = PSYN_CHEETAH>
 static int launch_eval_t(const EvalArgs& a, hipStream_t s) {
   using GE = RollGeo<NTO, 1>;
   const size_t lds = (size_t)GE::total * sizeof(float);
-  static const bool ok = hipFuncSetAttribute((const void*)k_eval<NTO, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  static const bool ok = hipFuncSetAttribute((const void*)k_eval<NTO, 1, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)lds) == hipSuccess;
   if (!ok) return -2;
-  hipLaunchKernelGGL((k_eval<NTO, 1>), dim3((a.nE + kRows - 1) / kRows), dim3(kActThreads), lds, s, a);
+  hipLaunchKernelGGL((k_eval<NTO, 1, KIND>), dim3((a.nE + kRows - 1) / kRows), dim3(kActThreads), lds, s, a);
   return 0;
 }
 
 int launch_eval(const EvalArgs& a, hipStream_t s) {
   if (eval_supported(a.K) != 0 || a.env.w.on || a.nE <= 0 || a.T <= 0) return -1;
   if (a.mode != PPO_SAMPLE && a.mode != PPO_MEAN && a.mode != PPO_ROACH) return -1;
+  if (a.env.kind == PSYN_PENDULUM) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_PENDULUM>(a, s) : -1;
+  if (a.env.kind != PSYN_CHEETAH) return -1;
   return a.K.OP == 16 ? launch_eval_t<1>(a, s) : launch_eval_t<2>(a, s);
 }

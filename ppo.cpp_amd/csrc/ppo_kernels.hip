@@ -13,9 +13,11 @@
 //   k_gae        GAE(lambda) (ppo:447-467) — op-for-op fp32, bit-exact with the reference formula
 //   k_perm / k_adv_*  minibatch permutation and (distributed) advantage statistics (ac:830-849)
 //   k_synth_*    synthetic HalfCheetah-shaped device env (bench/test env; not the hot path)
+//   k_pend_*     Pendulum-v1 device env, per-step form (the fused form is in ppo_rollout.hip / ppo_eval.hip)
 #include "ppo_agent.hpp"
 #include "ppo_kernels.hpp"
 #include "ppo_wrap.hpp"
+#include "ppo_pendulum_dev.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2429,6 +2431,80 @@ __global__ __launch_bounds__(256) void k_synth_step_wide(SynthArgs a, int e0, in
   a.autoreset[e] = tr ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PSYN_PENDULUM (Pendulum-v1, O = 3, A = 1): one lane per env. The vector-env bookkeeping
+// (next-step autoreset with reward 0 / done 0, episode statistics, wrapper chain) is k_synth_step's;
+// the dynamics are include/ppo_pendulum.h, bit for bit the host env gymcpp/pendulum.h.
+// ---------------------------------------------------------------------------------------------
+PPO_DEV void pend_store_obs(const SynthArgs& a, int e, float oc, const float* o3, float* obs) {
+  for (int i = 0; i < PEND_OBS_DIM; ++i)
+    obs[(long)e * PEND_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, PEND_OBS_DIM, i, oc, o3[i]) : o3[i];
+  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
+}
+
+__global__ __launch_bounds__(256) void k_pend_reset(SynthArgs a, int seed, float* obs, float* done) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
+  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+  float th, thd, o3[PEND_OBS_DIM];
+  pend_reset_dev(rc, rs, &th, &thd);
+  pend_obs(th, thd, o3);
+  float* q = a.q + (long)e * PEND_OBS_DIM;
+  q[0] = th; q[1] = thd; q[2] = 0.0f;
+  pend_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o3, obs);
+  a.rcount[e] = rc + 1;
+  a.t[e] = 0;
+  a.ep_ret[e] = 0.0f;
+  a.ep_len[e] = 0;
+  a.autoreset[e] = 0;
+  if (done) done[e] = 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_pend_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
+                                                   float lo, float hi, float* __restrict__ obs,
+                                                   float* __restrict__ reward, float* __restrict__ done) {
+#pragma clang fp contract(off)
+  const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= e1) return;
+  float* __restrict__ q = a.q + (long)e * PEND_OBS_DIM;
+  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
+  float th, thd, o3[PEND_OBS_DIM];
+  if (a.autoreset[e] != 0) {
+    const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+    pend_reset_dev(rc, rs, &th, &thd);
+    pend_obs(th, thd, o3);
+    q[0] = th; q[1] = thd;
+    pend_store_obs(a, e, oc, o3, obs);
+    a.rcount[e] = rc + 1;
+    a.t[e] = 0;
+    a.ep_ret[e] = 0.0f;
+    a.ep_len[e] = 0;
+    reward[e] = 0.0f;
+    done[e] = 0.0f;
+    a.autoreset[e] = 0;
+    return;
+  }
+  th = q[0]; thd = q[1];
+  const float ac = fminf(fmaxf(act[e - e0], lo), hi);  // clip_actions; the dynamics clip to +-2 themselves
+  const float r = pend_step(&th, &thd, ac, o3);
+  q[0] = th; q[1] = thd;
+  pend_store_obs(a, e, oc, o3, obs);
+  const int t = a.t[e] + 1;
+  a.t[e] = t;
+  const bool tr = t >= PEND_MAX_STEPS;
+  reward[e] = a.w.on ? wrap_reward(a.w, e, r, 0.0f) : r;  // Pendulum never terminates
+  done[e] = tr ? 1.0f : 0.0f;
+  a.ep_ret[e] = (a.ep_ret[e] + r);
+  a.ep_len[e] += 1;
+  if (tr) {
+    a.fin_ret[e] += a.ep_ret[e];
+    a.fin_len[e] += (float)a.ep_len[e];
+    a.fin_cnt[e] += 1.0f;
+  }
+  a.autoreset[e] = tr ? 1 : 0;
+}
+
 // =============================================================================================
 // explicit instantiations / launch wrappers
 // =============================================================================================
@@ -2668,10 +2744,19 @@ void launch_wrap_step(const WrapArgs& w, int O, int e0, int e1, float* obs, floa
   hipLaunchKernelGGL(k_wrap_step, dim3((e1 - e0 + 3) / 4), dim3(256), 0, s, w, O, e0, e1, obs, reward, term, is_reset);
 }
 void launch_synth_reset(const SynthArgs& a, int seed, float* obs, float* done, hipStream_t s) {
+  if (a.kind == PSYN_PENDULUM) {
+    hipLaunchKernelGGL(k_pend_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
+    return;
+  }
   hipLaunchKernelGGL(k_synth_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
 }
 void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, float lo, float hi, float* obs,
                        float* reward, float* done, hipStream_t s) {
+  if (a.kind == PSYN_PENDULUM) {
+    hipLaunchKernelGGL(k_pend_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
+                       done);
+    return;
+  }
   if (a.O > 32) {
     hipLaunchKernelGGL(k_synth_step_wide, dim3((e1 - e0 + 3) / 4), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs,
                        reward, done);

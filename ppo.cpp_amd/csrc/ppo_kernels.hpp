@@ -11,6 +11,7 @@
 #include "ppo_packed.hpp"
 
 #include "../../include/ppo_hip.h"
+#include "../../include/ppo_synth_env.h"
 
 struct ActArgs {
   const float* P;
@@ -258,7 +259,8 @@ struct WrapArgs {
 struct SynthArgs {
   WrapArgs w;  // applied inside the env's own kernels when w.on
   int E, O, A;
-  float* q;
+  int kind;    // PSYN_CHEETAH | PSYN_PENDULUM (include/ppo_synth_env.h)
+  float* q;    // [E][O] env state; Pendulum: theta, thetadot, one unused slot
   int* t;
   int* autoreset;
   uint32_t* rseed;

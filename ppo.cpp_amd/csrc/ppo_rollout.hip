@@ -19,6 +19,7 @@
 // (tests/test_gpu_rollout.py).
 #include "ppo_act_common.hpp"
 #include "ppo_wrap.hpp"
+#include "ppo_pendulum_dev.hpp"
 
 #include <type_traits>
 
@@ -58,8 +59,11 @@ constexpr int kRdbgEnv = 26;
 // =============================================================================================
 // k_rollout: T steps of {actor act + sample, synthetic env step} for 16 envs per workgroup
 // =============================================================================================
-template <int NTO, int NHT>
+// KIND: the device env's kind (PSYN_CHEETAH | PSYN_PENDULUM), a compile-time parameter so that the
+// cheetah instantiations carry nothing of the Pendulum step (and compile to the code they had)
+template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
+  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1");
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -210,8 +214,53 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
       a.s_logp[(long)t * E + row0 + tid] = lp;
     }
     ROLL_STAMP(t, 3);
-    // ---- env step (k_synth_step / k_synth_step_wide arithmetic): 32 lanes per env ----
-    {
+    // ---- env step: 32 lanes per env ----
+    if constexpr (KIND == PSYN_PENDULUM) {
+      // Pendulum-v1 (k_pend_step arithmetic): lane 0 of each env's lane group steps the env
+#pragma clang fp contract(off)
+      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float th, thd, o3[PEND_OBS_DIM];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          pend_reset_dev(rc, rs, &th, &thd);
+          pend_obs(th, thd, o3);
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EV[EV_DONE * R + r] = 0.0f;
+          EVI[EV_AR * R + r] = 0;
+          a.s_rewards[(long)t * E + e] = 0.0f;
+        } else {
+          th = q[0];
+          thd = q[1];
+          const float rw = pend_step(&th, &thd, fminf(fmaxf(ACT[r * 24], a.lo), a.hi), o3);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool tr = tt >= PEND_MAX_STEPS;
+          a.s_rewards[(long)t * E + e] = rw;
+          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (tr) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+          }
+          EVI[EV_AR * R + r] = tr ? 1 : 0;
+        }
+        q[0] = th;
+        q[1] = thd;
+#pragma unroll
+        for (int i = 0; i < PEND_OBS_DIM; ++i) xo[i] = o3[i];
+      }
+    } else {
+      // the synthetic cheetah (k_synth_step / k_synth_step_wide arithmetic)
 #pragma clang fp contract(off)
       const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
       const bool live = e < E;
@@ -488,8 +537,9 @@ PPO_DEV f4 trunk4(const f4 (&xv)[NKW], const f4 (&wa)[NKW][4], const f4 (&w2v)[4
 // no real row's arithmetic sees), the env / wrapper phase gets 256 / RR lanes per env. With RR = 4
 // a 1 024-env rollout spreads over 256 CUs instead of 64: the per-step layer MFMAs cost the same,
 // the VALU-bound wrapper chain a quarter.
-template <int NTO, int NHT, int RR>
+template <int NTO, int NHT, int RR, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
+  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1");
   constexpr int H = kR4H, R = RR, OP = NTO * 16, NKW = (NTO + 3) / 4, NHP = NHT * 16;
   constexpr int LPE = kR4Threads / RR;  // env lanes per env (one env within one wave)
   constexpr int LDQ = Roll4Geo<NTO, NHT>::LDQ, NCE = (OP + LPE - 1) / LPE, kEnvGroup = 12;
@@ -654,9 +704,61 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
       a.s_logp[(long)t * E + row0 + tid] = lp;
     }
     ROLL_STAMP(t, 3);
-    // ---- env step (k_synth_step / _wide arithmetic, wrapper chain fused): LPE lanes per env, all
-    // RR envs at once (the per-env reward / episode bookkeeping of lane 0 runs once per step) ----
-    {
+    // ---- env step (wrapper chain fused): LPE lanes per env, all RR envs at once (the per-env
+    // reward / episode bookkeeping of lane 0 runs once per step) ----
+    if constexpr (KIND == PSYN_PENDULUM) {
+      // Pendulum-v1 (k_pend_step arithmetic): lane 0 of each env's lane group steps the env
+#pragma clang fp contract(off)
+      const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float* om = WOM + r * LDQ;
+        float* ov = WOV + r * LDQ;
+        const float oc = EV[EV_WOC * R + r];
+        float th, thd, o3[PEND_OBS_DIM];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          pend_reset_dev(rc, rs, &th, &thd);
+          pend_obs(th, thd, o3);
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EV[EV_DONE * R + r] = 0.0f;
+          EVI[EV_AR * R + r] = 0;
+          a.s_rewards[(long)t * E + e] = 0.0f;
+        } else {
+          th = q[0];
+          thd = q[1];
+          const float rw = pend_step(&th, &thd, fminf(fmaxf(ACT[r * 32], a.lo), a.hi), o3);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool tr = tt >= PEND_MAX_STEPS;
+          a.s_rewards[(long)t * E + e] =
+              w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
+                                    EV + EV_WRC * R + r, w.gamma, rw, 0.0f)
+                   : rw;
+          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (tr) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+          }
+          EVI[EV_AR * R + r] = tr ? 1 : 0;
+        }
+        q[0] = th;
+        q[1] = thd;
+#pragma unroll
+        for (int i = 0; i < PEND_OBS_DIM; ++i) xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, o3[i]) : o3[i];
+        if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
+      }
+    } else {
+      // the synthetic cheetah (k_synth_step / _wide arithmetic)
 #pragma clang fp contract(off)
       const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
       if (e < E) {
@@ -1342,15 +1444,15 @@ int rollout_supported(const PackedLayout& K) {
 
 // 4 envs per workgroup while that still fits one workgroup per CU (the kernel's registers allow
 // one), 16 beyond
-template <int NTO, int NHT>
+template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 static int launch_rollout4_t(const RolloutArgs& a, hipStream_t s) {
   int dev = 0, ncu = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   if ((a.E + 3) / 4 <= ncu)
-    hipLaunchKernelGGL((k_rollout4<NTO, NHT, 4>), dim3((a.E + 3) / 4), dim3(kR4Threads), 0, s, a);
+    hipLaunchKernelGGL((k_rollout4<NTO, NHT, 4, KIND>), dim3((a.E + 3) / 4), dim3(kR4Threads), 0, s, a);
   else
-    hipLaunchKernelGGL((k_rollout4<NTO, NHT, 16>), dim3((a.E + 15) / 16), dim3(kR4Threads), 0, s, a);
+    hipLaunchKernelGGL((k_rollout4<NTO, NHT, 16, KIND>), dim3((a.E + 15) / 16), dim3(kR4Threads), 0, s, a);
   return 0;
 }
 template <int NTO>
@@ -1364,14 +1466,14 @@ static int launch_values4_t(const ValuesArgs& a, hipStream_t s) {
   return 0;
 }
 
-template <int NTO, int NHT>
+template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 static int launch_rollout_t(const RolloutArgs& a, hipStream_t s) {
   using GE = RollGeo<NTO, NHT>;
   const size_t lds = (size_t)GE::total * sizeof(float);
-  static const bool ok = hipFuncSetAttribute((const void*)k_rollout<NTO, NHT>,
+  static const bool ok = hipFuncSetAttribute((const void*)k_rollout<NTO, NHT, KIND>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   if (!ok) return -2;
-  hipLaunchKernelGGL((k_rollout<NTO, NHT>), dim3((a.E + kRows - 1) / kRows), dim3(kActThreads), lds, s, a);
+  hipLaunchKernelGGL((k_rollout<NTO, NHT, KIND>), dim3((a.E + kRows - 1) / kRows), dim3(kActThreads), lds, s, a);
   return 0;
 }
 
@@ -1386,8 +1488,10 @@ static int launch_rollout_v_t(const RolloutArgs& a, hipStream_t s) {
 }
 
 // the VALU rollout where it applies: AC agent, O <= 32, and few envs (auto: E <= 512, the N = 8
-// shard of the metric config); a.variant 1 forces k_rollout, 2 k_rollout_v
+// shard of the metric config); a.variant 1 forces k_rollout, 2 k_rollout_v. k_rollout_v steps the
+// synthetic cheetah only: a Pendulum env never takes it.
 static bool use_rollout_v(const RolloutArgs& a) {
+  if (a.env.kind != PSYN_CHEETAH) return false;
   if (a.K.kind != PPO_NET_LN_BETA || a.K.OP > 32 || a.env.w.on || !a.s_beta || a.variant == 1) return false;
   return a.variant == 2 || a.E <= 512;
 }
@@ -1395,7 +1499,15 @@ static bool use_rollout_v(const RolloutArgs& a) {
 int launch_rollout(const RolloutArgs& a, hipStream_t s) {
   if (rollout_supported(a.K) != 0) return -1;
   // an explicit rollout_kernel=valu that cannot apply is an error, not a silent k_rollout
+  if (a.variant == 2 && a.env.kind != PSYN_CHEETAH) return -4;
   if (a.variant == 2 && !use_rollout_v(a)) return -3;
+  if (a.env.kind == PSYN_PENDULUM) {  // O = 3, A = 1: one input tile, one head tile
+    if (a.K.OP != 16 || a.K.A != 1) return -1;
+    if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<1, 1, PSYN_PENDULUM>(a, s);
+    if (a.env.w.on) return -1;
+    return launch_rollout_t<1, 1, PSYN_PENDULUM>(a, s);
+  }
+  if (a.env.kind != PSYN_CHEETAH) return -1;
   if (use_rollout_v(a)) return a.K.OP == 16 ? launch_rollout_v_t<1>(a, s) : launch_rollout_v_t<2>(a, s);
   if (a.K.kind == PPO_NET_TANH_NORMAL) {
     const int nht = (a.K.A + 15) / 16;

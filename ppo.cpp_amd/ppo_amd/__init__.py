@@ -218,6 +218,8 @@ SYMBOLS = [
     ("ppo_profile_name", C.c_char_p, [_I]),
     ("ppo_profile_reset", _I, [_VP]),
     ("psyn_create", _I, [_I, _I, _I, C.POINTER(_VP)]),
+    ("psyn_create_env", _I, [C.c_char_p, _I, C.POINTER(_VP)]),
+    ("psyn_env_info", _I, [_VP, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     ("psyn_destroy", _I, [_VP]),
     ("psyn_reset", _I, [_VP, _I, _FP, _FP, _VP]),
     ("psyn_step", _I, [_VP, _I, _I, _FP, _F, _F, _FP, _FP, _FP, _VP]),
@@ -544,7 +546,12 @@ ENV_DIMS = {  # obs / act dims and action bounds of the reference's MuJoCo envs
     "Humanoid-v4": (376, 17, -0.4, 0.4),    # humanoid_v4.h:27-30
     "Ant-v5": (105, 8, -1.0, 1.0),          # ant_v5.h:38-41
     "Hopper-v5": (11, 3, -1.0, 1.0),        # hopper_v5.h:35-38
+    "Pendulum-v1": (3, 1, -2.0, 2.0),       # Gymnasium's pendulum.py; the one id with dynamics of its own
 }
+# env ids whose device env is created by id (psyn_create_env: an env kind of its own); every other id
+# runs the synthetic cheetah dynamics at the id's shape (psyn_create)
+DEVICE_ENV_KINDS = ("Pendulum-v1",)
+PSYN_CHEETAH, PSYN_PENDULUM = 0, 1
 
 
 @dataclass
@@ -1209,13 +1216,33 @@ def carla_ln_backward(z: "DeviceArray", gamma: "DeviceArray", stat: "DeviceArray
 
 
 class SynthEnv:
-    """Device-resident synthetic HalfCheetah-shaped vector env (include/ppo_synth_env.h)."""
+    """Device-resident vector env (include/ppo_synth_env.h): SynthEnv(E, obs_dim, act_dim) is the
+    synthetic HalfCheetah-shaped env; SynthEnv(E, env_id="Pendulum-v1") the env of that id
+    (psyn_create_env: "Pendulum-v1" | "SyntheticCheetah-v0")."""
 
-    def __init__(self, num_envs, obs_dim, act_dim):
+    def __init__(self, num_envs, obs_dim=None, act_dim=None, env_id=None):
         h = C.c_void_p()
-        check(lib().psyn_create(num_envs, obs_dim, act_dim, C.byref(h)))
+        if env_id is not None:
+            if obs_dim is not None or act_dim is not None:
+                raise ValueError("SynthEnv: pass env_id or (obs_dim, act_dim), not both")
+            check(lib().psyn_create_env(env_id.encode(), num_envs, C.byref(h)))
+        else:
+            if obs_dim is None or act_dim is None:
+                raise ValueError("SynthEnv: obs_dim and act_dim (or env_id) are required")
+            check(lib().psyn_create(num_envs, obs_dim, act_dim, C.byref(h)))
         self.h = h.value
-        self.E, self.O, self.A = num_envs, obs_dim, act_dim
+        self.E = num_envs
+        _, self.O, self.A, _ = self.info()
+
+    @classmethod
+    def make(cls, env_id, num_envs):
+        return cls(num_envs, env_id=env_id)
+
+    def info(self):
+        """(kind, obs_dim, act_dim, max_episode_steps) (psyn_env_info)"""
+        k, o, a, m = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(lib().psyn_env_info(self.h, C.byref(k), C.byref(o), C.byref(a), C.byref(m)))
+        return k.value, o.value, a.value, m.value
 
     def reset(self, seed, obs: DeviceArray, done: DeviceArray, stream=None):
         check(lib().psyn_reset(self.h, seed, obs.ptr, done.ptr, stream))
@@ -1307,7 +1334,7 @@ class Trainer:
             params = init_params(self.agent.layout, seed=cfg.seed, env_id=cfg.env_id)
         self.agent.load_params(params)
         E, O, A = self.hcfg.num_envs, self.hcfg.obs_dim, self.hcfg.act_dim
-        self.env = SynthEnv(E, O, A)
+        self.env = SynthEnv(E, env_id=cfg.env_id) if cfg.env_id in DEVICE_ENV_KINDS else SynthEnv(E, O, A)
         if cfg.env_id in ENV_DIMS:
             self.env.set_action_space(ENV_DIMS[cfg.env_id][2], ENV_DIMS[cfg.env_id][3])
         if wrappers is None:
@@ -1392,7 +1419,8 @@ def init_params(layout: Layout, seed=1, env_id=None, obs_mean=None, obs_std=None
             lo, hi = ENV_DIMS[env_id][2], ENV_DIMS[env_id][3]
         P[L.hi] = hi
         P[L.lo] = lo
-        if obs_mean is None and env_id in ENV_DIMS and ENV_DIMS[env_id][0] == O:
+        # (Pendulum-v1 has no table: ppo_obs_norm refuses it and the identity is used)
+        if obs_mean is None and env_id in ENV_DIMS and env_id not in DEVICE_ENV_KINDS and ENV_DIMS[env_id][0] == O:
             table = obs_norm(env_id)
             if table is not None:
                 obs_mean, obs_std = table
