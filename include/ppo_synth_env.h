@@ -17,6 +17,16 @@
  * Its state q [E, 3] holds theta, thetadot and one unused slot. The dynamics clip the torque to
  * [-2, 2] themselves, whatever psyn_set_action_space says. Not covered for this kind: the VALU
  * rollout kernel (rollout_kernel=valu is refused).
+ *
+ * A third kind, PSYN_CARTPOLE (psyn_create_env("CartPoleContinuous-v1")), is the first whose episodes
+ * terminate: Gymnasium's CartPole-v1 with the force 10 * clip(a, -1, 1) from one continuous action
+ * (O = 4: x, xdot, theta, thetadot, raw; A = 1; reward 1 per step; termination when |x| > 2.4 or
+ * |theta| > 12 degrees; truncation after 500 steps), with the arithmetic of include/ppo_cartpole.h —
+ * bit for bit the host env ppo.cpp_amd/gymcpp/cartpole.h. Its state q [E, 4] is the observation. The
+ * step's termination flag reaches NormalizeReward (the return accumulator restarts after a
+ * termination, not after a truncation); done = terminated or truncated, and psyn_step still returns
+ * done only. Episodes end on any step, on different steps in different envs. rollout_kernel=valu is
+ * refused for this kind as well.
  */
 #ifndef PPO_SYNTH_ENV_H
 #define PPO_SYNTH_ENV_H
@@ -29,12 +39,13 @@ typedef struct psyn_env psyn_t;
 
 int psyn_create(int num_envs, int obs_dim, int act_dim, psyn_t** out);
 /* The env kinds. psyn_create gives PSYN_CHEETAH at any (obs_dim, act_dim). */
-enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1 };
-/* By env id: "Pendulum-v1" (PSYN_PENDULUM: O = 3, A = 1, action space [-2, 2]) or
+enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1, PSYN_CARTPOLE = 2 };
+/* By env id: "Pendulum-v1" (PSYN_PENDULUM: O = 3, A = 1, action space [-2, 2]),
+ * "CartPoleContinuous-v1" (PSYN_CARTPOLE: O = 4, A = 1, action space [-1, 1]) or
  * "SyntheticCheetah-v0" (the env of psyn_create(num_envs, 17, 6)). Any other id, a NULL argument or
  * num_envs <= 0 is refused (-1, ppo_last_error lists the ids) before any HIP call. */
 int psyn_create_env(const char* env_id, int num_envs, psyn_t** out);
-/* kind, dims and the truncation step count (1000 | 200); any output may be NULL */
+/* kind, dims and the truncation step count (1000 | 200 | 500); any output may be NULL */
 int psyn_env_info(const psyn_t* env, int* kind, int* obs_dim, int* act_dim, int* max_steps);
 int psyn_destroy(psyn_t* env);
 /* reset(seed + i) for every env; writes obs [E,O] and done [E] (= 0) */
@@ -83,8 +94,11 @@ int ppo_set_rollout_mode(struct ppo_ctx* ctx, int mode);
  * *env_steps_out is that step + 1. PPO_SAMPLE draws with the key (seed, rank, env, step0 + k) at
  * evaluation step k, i.e. ppo_get_action_and_value(env_base = 0, step_id = step0 + k).
  *
- * The work runs on the context stream in chunks of chunk_steps env steps (0: 4096), one host
- * synchronisation per chunk; the chunk size changes no returned bit. For the AC agent (LayerNorm-Beta,
+ * The work runs on the context stream in chunks of chunk_steps env steps (0: 4096; 512 for
+ * PSYN_CARTPOLE), one host synchronisation per chunk; the chunk size changes no returned bit. The
+ * event buffer of a chunk holds every event the chunk can produce: an env finishes at most one episode
+ * per max_steps + 1 steps, and a PSYN_CARTPOLE env, whose episodes terminate, at most one per 2 steps
+ * (num_eval_envs * (chunk_steps / 2 + 2) events of 16 bytes: the reason for its shorter default). For the AC agent (LayerNorm-Beta,
  * hidden 256, obs_dim <= 32, act_dim <= 8) on an env without wrappers a chunk is one persistent launch
  * (k_eval: actor weights resident in registers, the env step fused in); otherwise, and with mode = 1,
  * it is chunk_steps x {act launch, psyn_step, event recorder}. Both give bitwise the same result.
@@ -101,7 +115,7 @@ typedef struct ppo_eval_config {
   int  num_eval_envs;   /* 1: ac:965-1001 (env 0 only); E: ppo:589-626 (all envs) */
   int  num_eval_runs;
   long step0;           /* Philox step id of evaluation step 0 (PPO_SAMPLE only) */
-  int  chunk_steps;     /* 0 = default; env steps per launch / per read-out */
+  int  chunk_steps;     /* 0 = default (4096; PSYN_CARTPOLE 512); env steps per launch / per read-out */
   int  mode;            /* 0 auto, 1 force the per-step path (tests, A/B) */
 } ppo_eval_config;
 

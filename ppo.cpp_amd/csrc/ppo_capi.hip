@@ -27,6 +27,7 @@
 #include "../../include/ppo_env_wrappers.h"
 #include "ppo_kernels.hpp"
 #include "../../include/ppo_pendulum.h"
+#include "../../include/ppo_cartpole.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -107,6 +108,7 @@ extern "C" int ppo_obs_norm(const char* env_id, const float** mean, const float*
   *mean = *stdv = nullptr;
   *n = 0;
   if (!strcmp(env_id, "HalfCheetah-v5")) return 0;  // zeros / ones (ac:510-511): identity
+  if (!strcmp(env_id, "CartPoleContinuous-v1")) return 0;  // raw (x, xdot, theta, thetadot): identity
   for (const ObsNormEntry& e : k_obs_norm)
     if (!strcmp(env_id, e.env_id)) {
       *mean = e.mean;
@@ -1688,8 +1690,13 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
   if (E <= 0) return fail("psyn_create_env: num_envs must be positive");
   const std::string id = env_id;
   if (id == "SyntheticCheetah-v0") return psyn_create(E, 17, 6, out);
+  if (id == "CartPoleContinuous-v1") {
+    if (int rc = psyn_create(E, CART_OBS_DIM, CART_ACT_DIM, out)) return rc;
+    (*out)->a.kind = PSYN_CARTPOLE;  // action space [-1, 1]: psyn_create's default
+    return 0;
+  }
   if (id != "Pendulum-v1")
-    return fail("psyn_create_env: unknown env_id " + id + " (Pendulum-v1, SyntheticCheetah-v0)");
+    return fail("psyn_create_env: unknown env_id " + id + " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1");
   if (int rc = psyn_create(E, PEND_OBS_DIM, PEND_ACT_DIM, out)) return rc;
   (*out)->a.kind = PSYN_PENDULUM;
   (*out)->act_lo = -PEND_MAX_TORQUE;
@@ -1699,7 +1706,14 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
   return 0;
 }
 
-static int psyn_max_steps(const psyn_t* env) { return env->a.kind == PSYN_PENDULUM ? PEND_MAX_STEPS : 1000; }
+static int psyn_max_steps(const psyn_t* env) {
+  return env->a.kind == PSYN_PENDULUM ? PEND_MAX_STEPS : env->a.kind == PSYN_CARTPOLE ? CART_MAX_STEPS : 1000;
+}
+static const char* psyn_kind_name(int kind) {
+  return kind == PSYN_PENDULUM ? "PSYN_PENDULUM (Pendulum-v1)"
+         : kind == PSYN_CARTPOLE ? "PSYN_CARTPOLE (CartPoleContinuous-v1)"
+                                 : "PSYN_CHEETAH";
+}
 
 extern "C" int psyn_env_info(const psyn_t* env, int* kind, int* obs_dim, int* act_dim, int* max_steps) {
   if (!env) return fail("psyn_env_info: null env");
@@ -1781,8 +1795,8 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
     {
       ProfScope ps(c, PK_ROLLOUT, c->stream);
       if (const int lrc = launch_rollout(r, c->stream))
-        return fail(lrc == -4 ? "ppo_rollout_synth: rollout_kernel=valu steps the synthetic cheetah only; this env's "
-                                "kind is PSYN_PENDULUM (Pendulum-v1): use rollout_kernel=auto or mfma"
+        return fail(lrc == -4 ? std::string("ppo_rollout_synth: rollout_kernel=valu steps the synthetic cheetah only; this env's "
+                                            "kind is ") + psyn_kind_name(env->a.kind) + ": use rollout_kernel=auto or mfma"
                     : lrc == -3 ? "ppo_rollout_synth: rollout_kernel=valu needs the LayerNorm-Beta agent, O <= 32 and no "
                                 "device env wrappers"
                               : "ppo_rollout_synth: rollout kernel launch failed");
@@ -1828,12 +1842,16 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
     return fail("Unsupported sample type used. Sample type: " + std::to_string(cfg->sample_type));
   if (O != c->K.O || A != c->K.A) return fail("ppo_evaluate_synth: env shape mismatch");
   if (cfg->chunk_steps < 0 || (cfg->mode != 0 && cfg->mode != 1)) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
-  const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : 4096;
+  // an env that terminates can finish an episode every other step, so its chunks are shorter by
+  // default (the event buffer below is sized for the worst case)
+  const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : (env->a.kind == PSYN_CARTPOLE ? 512 : 4096);
   const bool persistent = cfg->mode == 0 && eval_supported(c->K) == 0 && !env->a.w.on;
   // the env truncates after max_steps (1000; Pendulum 200) steps and resets on the next one: an env
   // finishes at most one episode per max_steps + 1 steps, which bounds the events of a chunk (an
-  // overflow is still detected)
-  const long devcap = (long)nE * (chunk / (psyn_max_steps(env) + 1) + 2);
+  // overflow is still detected). CartPoleContinuous-v1 terminates: an episode is at least one step
+  // and the reset step after it, so an env finishes at most one episode per 2 steps.
+  const int min_period = env->a.kind == PSYN_CARTPOLE ? 2 : psyn_max_steps(env) + 1;
+  const long devcap = (long)nE * (chunk / min_period + 2);
   hipStream_t s = c->stream;
   struct Scratch {
     char* p = nullptr;

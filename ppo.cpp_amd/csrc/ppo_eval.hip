@@ -13,11 +13,12 @@
 // (step, env) (ppo_eval_events.hpp).
 #include "ppo_rollout_common.hpp"
 #include "ppo_pendulum_dev.hpp"
+#include "ppo_cartpole_dev.hpp"
 
 // KIND: the device env's kind, compile-time as in k_rollout
 template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
-  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1");
+  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1");
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -158,6 +159,50 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
 #pragma unroll
         for (int i = 0; i < PEND_OBS_DIM; ++i) xo[i] = o3[i];
       }
+    } else if constexpr (KIND == PSYN_CARTPOLE) {
+      // CartPoleContinuous-v1 (k_cart_step arithmetic): lane 0 of each env's lane group steps the
+      // env; an episode that terminates or is truncated, on whatever step, is one event
+#pragma clang fp contract(off)
+      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float s4[CART_OBS_DIM];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          cart_reset_dev(rc, rs, s4);
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EVI[EV_AR * R + r] = 0;
+        } else {
+#pragma unroll
+          for (int i = 0; i < CART_OBS_DIM; ++i) s4[i] = q[i];
+          float te;
+          const float rw = cart_step(s4, fminf(fmaxf(ACT[r * 24], a.lo), a.hi), &te);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool fin = (te != 0.0f) || tt >= CART_MAX_STEPS;  // done = terminated or truncated
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (fin) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+            const unsigned slot = atomicAdd(a.count, 1u);
+            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
+          }
+          EVI[EV_AR * R + r] = fin ? 1 : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < CART_OBS_DIM; ++i) {
+          q[i] = s4[i];
+          xo[i] = s4[i];
+        }
+      }
     } else {
       // the synthetic cheetah (k_synth_step arithmetic)
 #pragma clang fp contract(off)
@@ -292,6 +337,7 @@ int launch_eval(const EvalArgs& a, hipStream_t s) {
   if (eval_supported(a.K) != 0 || a.env.w.on || a.nE <= 0 || a.T <= 0) return -1;
   if (a.mode != PPO_SAMPLE && a.mode != PPO_MEAN && a.mode != PPO_ROACH) return -1;
   if (a.env.kind == PSYN_PENDULUM) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_PENDULUM>(a, s) : -1;
+  if (a.env.kind == PSYN_CARTPOLE) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_CARTPOLE>(a, s) : -1;
   if (a.env.kind != PSYN_CHEETAH) return -1;
   return a.K.OP == 16 ? launch_eval_t<1>(a, s) : launch_eval_t<2>(a, s);
 }

@@ -14,10 +14,12 @@
 //   k_perm / k_adv_*  minibatch permutation and (distributed) advantage statistics (ac:830-849)
 //   k_synth_*    synthetic HalfCheetah-shaped device env (bench/test env; not the hot path)
 //   k_pend_*     Pendulum-v1 device env, per-step form (the fused form is in ppo_rollout.hip / ppo_eval.hip)
+//   k_cart_*     CartPoleContinuous-v1 device env (it terminates), per-step form (fused form: as k_pend_*)
 #include "ppo_agent.hpp"
 #include "ppo_kernels.hpp"
 #include "ppo_wrap.hpp"
 #include "ppo_pendulum_dev.hpp"
+#include "ppo_cartpole_dev.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2505,6 +2507,80 @@ __global__ __launch_bounds__(256) void k_pend_step(SynthArgs a, int e0, int e1, 
   a.autoreset[e] = tr ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PSYN_CARTPOLE (CartPoleContinuous-v1, O = 4, A = 1): one lane per env, the bookkeeping of
+// k_pend_step with one difference: the episodes terminate. The step's termination flag te goes to
+// NormalizeReward (wrap_reward), done = te or truncated, and an episode is finished (statistics,
+// autoreset) on either. The dynamics are include/ppo_cartpole.h, bit for bit gymcpp/cartpole.h.
+// ---------------------------------------------------------------------------------------------
+PPO_DEV void cart_store_obs(const SynthArgs& a, int e, float oc, const float* s4, float* obs) {
+  for (int i = 0; i < CART_OBS_DIM; ++i)
+    obs[(long)e * CART_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, CART_OBS_DIM, i, oc, s4[i]) : s4[i];
+  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
+}
+
+__global__ __launch_bounds__(256) void k_cart_reset(SynthArgs a, int seed, float* obs, float* done) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
+  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+  float s4[CART_OBS_DIM];
+  cart_reset_dev(rc, rs, s4);
+  float* q = a.q + (long)e * CART_OBS_DIM;
+  for (int i = 0; i < CART_OBS_DIM; ++i) q[i] = s4[i];
+  cart_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, s4, obs);
+  a.rcount[e] = rc + 1;
+  a.t[e] = 0;
+  a.ep_ret[e] = 0.0f;
+  a.ep_len[e] = 0;
+  a.autoreset[e] = 0;
+  if (done) done[e] = 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_cart_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
+                                                   float lo, float hi, float* __restrict__ obs,
+                                                   float* __restrict__ reward, float* __restrict__ done) {
+#pragma clang fp contract(off)
+  const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= e1) return;
+  float* __restrict__ q = a.q + (long)e * CART_OBS_DIM;
+  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
+  float s4[CART_OBS_DIM];
+  if (a.autoreset[e] != 0) {
+    const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+    cart_reset_dev(rc, rs, s4);
+    for (int i = 0; i < CART_OBS_DIM; ++i) q[i] = s4[i];
+    cart_store_obs(a, e, oc, s4, obs);
+    a.rcount[e] = rc + 1;
+    a.t[e] = 0;
+    a.ep_ret[e] = 0.0f;
+    a.ep_len[e] = 0;
+    reward[e] = 0.0f;
+    done[e] = 0.0f;
+    a.autoreset[e] = 0;
+    return;
+  }
+  for (int i = 0; i < CART_OBS_DIM; ++i) s4[i] = q[i];
+  const float ac = fminf(fmaxf(act[e - e0], lo), hi);  // clip_actions; the dynamics clip to +-1 themselves
+  float te;
+  const float r = cart_step(s4, ac, &te);
+  for (int i = 0; i < CART_OBS_DIM; ++i) q[i] = s4[i];
+  cart_store_obs(a, e, oc, s4, obs);
+  const int t = a.t[e] + 1;
+  a.t[e] = t;
+  const bool fin = (te != 0.0f) || t >= CART_MAX_STEPS;  // done = terminated or truncated
+  reward[e] = a.w.on ? wrap_reward(a.w, e, r, te) : r;
+  done[e] = fin ? 1.0f : 0.0f;
+  a.ep_ret[e] = (a.ep_ret[e] + r);
+  a.ep_len[e] += 1;
+  if (fin) {
+    a.fin_ret[e] += a.ep_ret[e];
+    a.fin_len[e] += (float)a.ep_len[e];
+    a.fin_cnt[e] += 1.0f;
+  }
+  a.autoreset[e] = fin ? 1 : 0;
+}
+
 // =============================================================================================
 // explicit instantiations / launch wrappers
 // =============================================================================================
@@ -2748,12 +2824,21 @@ void launch_synth_reset(const SynthArgs& a, int seed, float* obs, float* done, h
     hipLaunchKernelGGL(k_pend_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
     return;
   }
+  if (a.kind == PSYN_CARTPOLE) {
+    hipLaunchKernelGGL(k_cart_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
+    return;
+  }
   hipLaunchKernelGGL(k_synth_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
 }
 void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, float lo, float hi, float* obs,
                        float* reward, float* done, hipStream_t s) {
   if (a.kind == PSYN_PENDULUM) {
     hipLaunchKernelGGL(k_pend_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
+                       done);
+    return;
+  }
+  if (a.kind == PSYN_CARTPOLE) {
+    hipLaunchKernelGGL(k_cart_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
                        done);
     return;
   }

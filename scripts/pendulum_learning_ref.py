@@ -84,11 +84,13 @@ class HostPendulum:
 
 
 class WrappedEnv:
-    """The env the trainer sees: the host Pendulum, under the PPO wrapper chain for the PPO agent."""
+    """The env the trainer sees: the host env (HostPendulum, or another class with its interface whose
+    step() may also return the termination flags, after the rewards), under the PPO wrapper chain for
+    the PPO agent."""
 
-    def __init__(self, E, wrapped, gamma):
-        self.env = HostPendulum(E)
-        self.wrap = O.VecWrappers(E, OD, gamma) if wrapped else None
+    def __init__(self, E, wrapped, gamma, host=HostPendulum, od=OD):
+        self.env = host(E)
+        self.wrap = O.VecWrappers(E, od, gamma) if wrapped else None
         self.was_done = np.zeros(E, np.float32)
 
     def reset(self, seed):
@@ -97,9 +99,11 @@ class WrappedEnv:
         return self.wrap.reset(obs) if self.wrap else obs
 
     def step(self, act):
-        obs, rew, done, ret, ln = self.env.step(act)
+        out = self.env.step(act)
+        obs, rew, done, ret, ln = out if len(out) == 5 else out[:2] + out[3:]
+        term = np.zeros_like(rew) if len(out) == 5 else out[2]  # Pendulum never terminates
         if self.wrap:  # the step after a done is the autoreset: its reward (0) bypasses NormalizeReward
-            obs, rew = self.wrap.step(obs, rew, np.zeros_like(rew), self.was_done)
+            obs, rew = self.wrap.step(obs, rew, term, self.was_done)
         self.was_done = done
         return obs, rew, done, ret, ln
 
@@ -119,15 +123,17 @@ def evaluate(env, L, p, eval_seed):
     return float(np.mean(rets)), len(rets)
 
 
-def run_seed(a, seed, curve=False, max_iters=None, want_params=False):
-    """max_iters / want_params: stop early and return the parameters (to compare one iteration with the GPU)."""
+def run_seed(a, seed, curve=False, max_iters=None, want_params=False, env_id=ENV, dims=(OD, AD), host=HostPendulum):
+    """max_iters / want_params: stop early and return the parameters (to compare one iteration with the GPU).
+    env_id / dims / host: the task (scripts/cartpole_learning_ref.py runs this loop over its own host env)."""
+    ENV, (OD, AD) = env_id, dims
     import ppo_amd
     kind = ppo_amd.PPO_NET_TANH_NORMAL if a.agent == "ppo" else ppo_amd.PPO_NET_LN_BETA
     H = 64 if a.agent == "ppo" else 256
     E, T = a.num_envs, a.num_steps
     L = O.layout_init(kind, OD, AD, H)
     p = ppo_amd.init_params(ppo_amd.agent_layout(kind, OD, AD, H), seed=seed, env_id=ENV)
-    env = WrappedEnv(E, a.agent == "ppo", a.gamma)
+    env = WrappedEnv(E, a.agent == "ppo", a.gamma, host, OD)
     env.reset(seed)  # Trainer's constructor resets the env once (the observation normaliser sees it)
     untrained, n_eval = evaluate(env, L, p, a.eval_seed)
     obs = env.reset(seed)
@@ -188,10 +194,10 @@ def parser():
     return ap
 
 
-def main():
-    a = parser().parse_args()
+def main(a=None, env_id=ENV, dims=(OD, AD), host=HostPendulum):
+    a = a or parser().parse_args()
     t0 = time.time()
-    runs = [run_seed(a, s, a.curve) for s in a.seeds]
+    runs = [run_seed(a, s, a.curve, env_id=env_id, dims=dims, host=host) for s in a.seeds]
     un = [r["untrained"] for r in runs]
     spread = max(un) - min(un)
     imp = [r["trained"] - r["untrained"] for r in runs]
@@ -199,7 +205,7 @@ def main():
     cfg = {k: getattr(a, k) for k in ("agent", "eval_seed", "num_envs", "num_steps", "total_timesteps", "num_minibatches",
                                       "update_epochs", "learning_rate", "gamma", "gae_lambda", "clip_coef", "ent_coef",
                                       "vf_coef", "max_grad_norm", "adam_eps")}
-    out = {"env_id": ENV, "config": cfg, "seeds": a.seeds, "runs": runs, "untrained_spread": spread,
+    out = {"env_id": env_id, "config": cfg, "seeds": a.seeds, "runs": runs, "untrained_spread": spread,
            "min_improvement": min(imp), "condition_met": ok, "eval_episodes": EVAL_EPISODES,
            "date": datetime.date.today().isoformat()}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
