@@ -27,6 +27,17 @@
  * termination, not after a truncation); done = terminated or truncated, and psyn_step still returns
  * done only. Episodes end on any step, on different steps in different envs. rollout_kernel=valu is
  * refused for this kind as well.
+ *
+ * A fourth kind, PSYN_REACHER (psyn_create_env("ReacherPlanar-v0")), is the first real task with a
+ * two-dimensional action: a two-link planar arm, O = 10, A = 2, action space [-1, 1] per dimension,
+ * truncation after 50 steps, never terminates. It is not MuJoCo's Reacher: it takes Gymnasium
+ * Reacher-v5's task definition (observation layout, reward, goal distribution, truncation, action
+ * space) and puts the textbook two-link manipulator equations under it, with the arithmetic of
+ * include/ppo_reacher.h — bit for bit the host env ppo.cpp_amd/gymcpp/reacher.h. Its state q [E, 10]
+ * holds q1, q2, q1dot, q2dot, gx, gy and four unused slots. The goal (gx, gy) is env state that no step
+ * touches: it survives every step and is redrawn at every autoreset. The dynamics clip both actions to
+ * [-1, 1] themselves; the termination flag passed to the wrapper chain is always 0. Not covered for
+ * this kind: the VALU rollout kernel (rollout_kernel=valu is refused).
  */
 #ifndef PPO_SYNTH_ENV_H
 #define PPO_SYNTH_ENV_H
@@ -39,13 +50,14 @@ typedef struct psyn_env psyn_t;
 
 int psyn_create(int num_envs, int obs_dim, int act_dim, psyn_t** out);
 /* The env kinds. psyn_create gives PSYN_CHEETAH at any (obs_dim, act_dim). */
-enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1, PSYN_CARTPOLE = 2 };
+enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1, PSYN_CARTPOLE = 2, PSYN_REACHER = 3 };
 /* By env id: "Pendulum-v1" (PSYN_PENDULUM: O = 3, A = 1, action space [-2, 2]),
- * "CartPoleContinuous-v1" (PSYN_CARTPOLE: O = 4, A = 1, action space [-1, 1]) or
+ * "CartPoleContinuous-v1" (PSYN_CARTPOLE: O = 4, A = 1, action space [-1, 1]),
+ * "ReacherPlanar-v0" (PSYN_REACHER: O = 10, A = 2, action space [-1, 1]^2) or
  * "SyntheticCheetah-v0" (the env of psyn_create(num_envs, 17, 6)). Any other id, a NULL argument or
  * num_envs <= 0 is refused (-1, ppo_last_error lists the ids) before any HIP call. */
 int psyn_create_env(const char* env_id, int num_envs, psyn_t** out);
-/* kind, dims and the truncation step count (1000 | 200 | 500); any output may be NULL */
+/* kind, dims and the truncation step count (1000 | 200 | 500 | 50); any output may be NULL */
 int psyn_env_info(const psyn_t* env, int* kind, int* obs_dim, int* act_dim, int* max_steps);
 int psyn_destroy(psyn_t* env);
 /* reset(seed + i) for every env; writes obs [E,O] and done [E] (= 0) */

@@ -28,6 +28,7 @@
 #include "ppo_kernels.hpp"
 #include "../../include/ppo_pendulum.h"
 #include "../../include/ppo_cartpole.h"
+#include "../../include/ppo_reacher.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -109,6 +110,7 @@ extern "C" int ppo_obs_norm(const char* env_id, const float** mean, const float*
   *n = 0;
   if (!strcmp(env_id, "HalfCheetah-v5")) return 0;  // zeros / ones (ac:510-511): identity
   if (!strcmp(env_id, "CartPoleContinuous-v1")) return 0;  // raw (x, xdot, theta, thetadot): identity
+  if (!strcmp(env_id, "ReacherPlanar-v0")) return 0;       // all ten values are of order 1 or smaller: identity
   for (const ObsNormEntry& e : k_obs_norm)
     if (!strcmp(env_id, e.env_id)) {
       *mean = e.mean;
@@ -1695,8 +1697,17 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
     (*out)->a.kind = PSYN_CARTPOLE;  // action space [-1, 1]: psyn_create's default
     return 0;
   }
+  if (id == "ReacherPlanar-v0") {
+    if (int rc = psyn_create(E, REACH_OBS_DIM, REACH_ACT_DIM, out)) return rc;
+    (*out)->a.kind = PSYN_REACHER;  // action space [-1, 1]: psyn_create's default
+    // q [E, 10] holds q1, q2, q1dot, q2dot, gx, gy; the four unused slots are defined from the start
+    // (the persistent kernels carry them along)
+    HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * REACH_OBS_DIM));
+    return 0;
+  }
   if (id != "Pendulum-v1")
-    return fail("psyn_create_env: unknown env_id " + id + " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1");
+    return fail("psyn_create_env: unknown env_id " + id +
+                " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1, ReacherPlanar-v0");
   if (int rc = psyn_create(E, PEND_OBS_DIM, PEND_ACT_DIM, out)) return rc;
   (*out)->a.kind = PSYN_PENDULUM;
   (*out)->act_lo = -PEND_MAX_TORQUE;
@@ -1707,11 +1718,15 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
 }
 
 static int psyn_max_steps(const psyn_t* env) {
-  return env->a.kind == PSYN_PENDULUM ? PEND_MAX_STEPS : env->a.kind == PSYN_CARTPOLE ? CART_MAX_STEPS : 1000;
+  return env->a.kind == PSYN_PENDULUM   ? PEND_MAX_STEPS
+         : env->a.kind == PSYN_CARTPOLE ? CART_MAX_STEPS
+         : env->a.kind == PSYN_REACHER  ? REACH_MAX_STEPS
+                                        : 1000;
 }
 static const char* psyn_kind_name(int kind) {
   return kind == PSYN_PENDULUM ? "PSYN_PENDULUM (Pendulum-v1)"
          : kind == PSYN_CARTPOLE ? "PSYN_CARTPOLE (CartPoleContinuous-v1)"
+         : kind == PSYN_REACHER  ? "PSYN_REACHER (ReacherPlanar-v0)"
                                  : "PSYN_CHEETAH";
 }
 

@@ -14,11 +14,13 @@
 #include "ppo_rollout_common.hpp"
 #include "ppo_pendulum_dev.hpp"
 #include "ppo_cartpole_dev.hpp"
+#include "ppo_reacher_dev.hpp"
 
 // KIND: the device env's kind, compile-time as in k_rollout
 template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
-  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1");
+  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1),
+                "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1; ReacherPlanar-v0: O = 10, A = 2");
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -203,6 +205,54 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
           xo[i] = s4[i];
         }
       }
+    } else if constexpr (KIND == PSYN_REACHER) {
+      // ReacherPlanar-v0 (k_reach_step arithmetic): lane 0 of each env's lane group steps the env
+      // from both of its actions, ACT[r * 24 + 0] and [+ 1] (written by other lanes before the
+      // barrier above). The goal slots q[4], q[5] are written by a reset only.
+#pragma clang fp contract(off)
+      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          reach_reset_dev(rc, rs, s6);
+          reach_obs(s6, o10);
+          q[4] = s6[4];  // a new goal with the new episode
+          q[5] = s6[5];
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EVI[EV_AR * R + r] = 0;
+        } else {
+#pragma unroll
+          for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
+          const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi),
+                                           fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi)};
+          const float rw = reach_step(s6, ac, o10);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool tr = tt >= REACH_MAX_STEPS;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (tr) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+            const unsigned slot = atomicAdd(a.count, 1u);
+            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
+          }
+          EVI[EV_AR * R + r] = tr ? 1 : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = s6[i];
+#pragma unroll
+        for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = o10[i];
+      }
     } else {
       // the synthetic cheetah (k_synth_step arithmetic)
 #pragma clang fp contract(off)
@@ -338,6 +388,8 @@ int launch_eval(const EvalArgs& a, hipStream_t s) {
   if (a.mode != PPO_SAMPLE && a.mode != PPO_MEAN && a.mode != PPO_ROACH) return -1;
   if (a.env.kind == PSYN_PENDULUM) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_PENDULUM>(a, s) : -1;
   if (a.env.kind == PSYN_CARTPOLE) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_CARTPOLE>(a, s) : -1;
+  if (a.env.kind == PSYN_REACHER)
+    return (a.K.OP == 16 && a.K.A == REACH_ACT_DIM) ? launch_eval_t<1, PSYN_REACHER>(a, s) : -1;
   if (a.env.kind != PSYN_CHEETAH) return -1;
   return a.K.OP == 16 ? launch_eval_t<1>(a, s) : launch_eval_t<2>(a, s);
 }

@@ -15,11 +15,13 @@
 //   k_synth_*    synthetic HalfCheetah-shaped device env (bench/test env; not the hot path)
 //   k_pend_*     Pendulum-v1 device env, per-step form (the fused form is in ppo_rollout.hip / ppo_eval.hip)
 //   k_cart_*     CartPoleContinuous-v1 device env (it terminates), per-step form (fused form: as k_pend_*)
+//   k_reach_*    ReacherPlanar-v0 device env (O = 10, A = 2, a goal per episode), per-step form (fused form: as k_pend_*)
 #include "ppo_agent.hpp"
 #include "ppo_kernels.hpp"
 #include "ppo_wrap.hpp"
 #include "ppo_pendulum_dev.hpp"
 #include "ppo_cartpole_dev.hpp"
+#include "ppo_reacher_dev.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2581,6 +2583,84 @@ __global__ __launch_bounds__(256) void k_cart_step(SynthArgs a, int e0, int e1, 
   a.autoreset[e] = fin ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PSYN_REACHER (ReacherPlanar-v0, O = 10, A = 2): one lane per env, the bookkeeping of k_cart_step.
+// The episodes never terminate (the flag passed to wrap_reward is 0; done = truncated after 50
+// steps). The state q[0..5] = (q1, q2, q1dot, q2dot, gx, gy); the goal slots are written by a reset
+// only. The step reads both actions of the env. The dynamics are include/ppo_reacher.h, bit for
+// bit gymcpp/reacher.h.
+// ---------------------------------------------------------------------------------------------
+PPO_DEV void reach_store_obs(const SynthArgs& a, int e, float oc, const float* o10, float* obs) {
+  for (int i = 0; i < REACH_OBS_DIM; ++i)
+    obs[(long)e * REACH_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, REACH_OBS_DIM, i, oc, o10[i]) : o10[i];
+  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
+}
+
+__global__ __launch_bounds__(256) void k_reach_reset(SynthArgs a, int seed, float* obs, float* done) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
+  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+  float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
+  reach_reset_dev(rc, rs, s6);
+  reach_obs(s6, o10);
+  float* q = a.q + (long)e * REACH_OBS_DIM;
+  for (int i = 0; i < REACH_STATE_DIM; ++i) q[i] = s6[i];
+  reach_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o10, obs);
+  a.rcount[e] = rc + 1;
+  a.t[e] = 0;
+  a.ep_ret[e] = 0.0f;
+  a.ep_len[e] = 0;
+  a.autoreset[e] = 0;
+  if (done) done[e] = 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_reach_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
+                                                    float lo, float hi, float* __restrict__ obs,
+                                                    float* __restrict__ reward, float* __restrict__ done) {
+#pragma clang fp contract(off)
+  const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= e1) return;
+  float* __restrict__ q = a.q + (long)e * REACH_OBS_DIM;
+  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
+  float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
+  if (a.autoreset[e] != 0) {
+    const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+    reach_reset_dev(rc, rs, s6);
+    reach_obs(s6, o10);
+    for (int i = 0; i < REACH_STATE_DIM; ++i) q[i] = s6[i];  // a new goal with the new episode
+    reach_store_obs(a, e, oc, o10, obs);
+    a.rcount[e] = rc + 1;
+    a.t[e] = 0;
+    a.ep_ret[e] = 0.0f;
+    a.ep_len[e] = 0;
+    reward[e] = 0.0f;
+    done[e] = 0.0f;
+    a.autoreset[e] = 0;
+    return;
+  }
+  for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
+  const float* __restrict__ ar = act + (long)(e - e0) * REACH_ACT_DIM;
+  // clip_actions, per dimension; the dynamics clip to +-1 themselves
+  const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ar[0], lo), hi), fminf(fmaxf(ar[1], lo), hi)};
+  const float r = reach_step(s6, ac, o10);
+  for (int i = 0; i < 4; ++i) q[i] = s6[i];  // the goal slots stay as the reset wrote them
+  reach_store_obs(a, e, oc, o10, obs);
+  const int t = a.t[e] + 1;
+  a.t[e] = t;
+  const bool tr = t >= REACH_MAX_STEPS;
+  reward[e] = a.w.on ? wrap_reward(a.w, e, r, 0.0f) : r;  // the arm never terminates
+  done[e] = tr ? 1.0f : 0.0f;
+  a.ep_ret[e] = (a.ep_ret[e] + r);
+  a.ep_len[e] += 1;
+  if (tr) {
+    a.fin_ret[e] += a.ep_ret[e];
+    a.fin_len[e] += (float)a.ep_len[e];
+    a.fin_cnt[e] += 1.0f;
+  }
+  a.autoreset[e] = tr ? 1 : 0;
+}
+
 // =============================================================================================
 // explicit instantiations / launch wrappers
 // =============================================================================================
@@ -2828,6 +2908,10 @@ void launch_synth_reset(const SynthArgs& a, int seed, float* obs, float* done, h
     hipLaunchKernelGGL(k_cart_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
     return;
   }
+  if (a.kind == PSYN_REACHER) {
+    hipLaunchKernelGGL(k_reach_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
+    return;
+  }
   hipLaunchKernelGGL(k_synth_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
 }
 void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, float lo, float hi, float* obs,
@@ -2839,6 +2923,11 @@ void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, flo
   }
   if (a.kind == PSYN_CARTPOLE) {
     hipLaunchKernelGGL(k_cart_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
+                       done);
+    return;
+  }
+  if (a.kind == PSYN_REACHER) {
+    hipLaunchKernelGGL(k_reach_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
                        done);
     return;
   }

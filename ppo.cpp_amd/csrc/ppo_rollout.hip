@@ -21,6 +21,7 @@
 #include "ppo_wrap.hpp"
 #include "ppo_pendulum_dev.hpp"
 #include "ppo_cartpole_dev.hpp"
+#include "ppo_reacher_dev.hpp"
 
 #include <type_traits>
 
@@ -60,12 +61,13 @@ constexpr int kRdbgEnv = 26;
 // =============================================================================================
 // k_rollout: T steps of {actor act + sample, synthetic env step} for 16 envs per workgroup
 // =============================================================================================
-// KIND: the device env's kind (PSYN_CHEETAH | PSYN_PENDULUM | PSYN_CARTPOLE), a compile-time
-// parameter so that the cheetah instantiations carry nothing of the Pendulum or CartPole step (and
-// compile to the code they had)
+// KIND: the device env's kind (PSYN_CHEETAH | PSYN_PENDULUM | PSYN_CARTPOLE | PSYN_REACHER), a
+// compile-time parameter so that the cheetah instantiations carry nothing of the Pendulum, CartPole
+// or Reacher step (and compile to the code they had)
 template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
-  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1");
+  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1),
+                "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1; ReacherPlanar-v0: O = 10, A = 2");
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -306,6 +308,56 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
           q[i] = s4[i];
           xo[i] = s4[i];
         }
+      }
+    } else if constexpr (KIND == PSYN_REACHER) {
+      // ReacherPlanar-v0 (k_reach_step arithmetic): lane 0 of each env's lane group steps the env
+      // from both of its actions, ACT[r * 24 + 0] and [+ 1] (written by other lanes before the
+      // barrier above). The goal slots q[4], q[5] are written by a reset only.
+#pragma clang fp contract(off)
+      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          reach_reset_dev(rc, rs, s6);
+          reach_obs(s6, o10);
+          q[4] = s6[4];  // a new goal with the new episode
+          q[5] = s6[5];
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EV[EV_DONE * R + r] = 0.0f;
+          EVI[EV_AR * R + r] = 0;
+          a.s_rewards[(long)t * E + e] = 0.0f;
+        } else {
+#pragma unroll
+          for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
+          const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi),
+                                           fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi)};
+          const float rw = reach_step(s6, ac, o10);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool tr = tt >= REACH_MAX_STEPS;
+          a.s_rewards[(long)t * E + e] = rw;
+          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (tr) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+          }
+          EVI[EV_AR * R + r] = tr ? 1 : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = s6[i];
+#pragma unroll
+        for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = o10[i];
       }
     } else {
       // the synthetic cheetah (k_synth_step / k_synth_step_wide arithmetic)
@@ -587,7 +639,8 @@ PPO_DEV f4 trunk4(const f4 (&xv)[NKW], const f4 (&wa)[NKW][4], const f4 (&w2v)[4
 // the VALU-bound wrapper chain a quarter.
 template <int NTO, int NHT, int RR, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
-  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1), "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1");
+  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1),
+                "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1; ReacherPlanar-v0: O = 10, A = 2");
   constexpr int H = kR4H, R = RR, OP = NTO * 16, NKW = (NTO + 3) / 4, NHP = NHT * 16;
   constexpr int LPE = kR4Threads / RR;  // env lanes per env (one env within one wave)
   constexpr int LDQ = Roll4Geo<NTO, NHT>::LDQ, NCE = (OP + LPE - 1) / LPE, kEnvGroup = 12;
@@ -857,6 +910,64 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
           q[i] = s4[i];
           xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, s4[i]) : s4[i];
         }
+        if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
+      }
+    } else if constexpr (KIND == PSYN_REACHER) {
+      // ReacherPlanar-v0 (k_reach_step arithmetic): lane 0 of each env's lane group steps the env
+      // from both of its actions, ACT[r * 32 + 0] and [+ 1] (written by other lanes before the
+      // barrier above). The goal slots q[4], q[5] are written by a reset only. The termination
+      // flag passed to NormalizeReward is always 0.
+#pragma clang fp contract(off)
+      const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float* om = WOM + r * LDQ;
+        float* ov = WOV + r * LDQ;
+        const float oc = EV[EV_WOC * R + r];
+        float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          reach_reset_dev(rc, rs, s6);
+          reach_obs(s6, o10);
+          q[4] = s6[4];  // a new goal with the new episode
+          q[5] = s6[5];
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EV[EV_DONE * R + r] = 0.0f;
+          EVI[EV_AR * R + r] = 0;
+          a.s_rewards[(long)t * E + e] = 0.0f;
+        } else {
+#pragma unroll
+          for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
+          const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ACT[r * 32 + 0], a.lo), a.hi),
+                                           fminf(fmaxf(ACT[r * 32 + 1], a.lo), a.hi)};
+          const float rw = reach_step(s6, ac, o10);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool tr = tt >= REACH_MAX_STEPS;
+          a.s_rewards[(long)t * E + e] =
+              w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
+                                    EV + EV_WRC * R + r, w.gamma, rw, 0.0f)
+                   : rw;
+          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (tr) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+          }
+          EVI[EV_AR * R + r] = tr ? 1 : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = s6[i];
+#pragma unroll
+        for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, o10[i]) : o10[i];
         if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
       }
     } else {
@@ -1591,7 +1702,7 @@ static int launch_rollout_v_t(const RolloutArgs& a, hipStream_t s) {
 
 // the VALU rollout where it applies: AC agent, O <= 32, and few envs (auto: E <= 512, the N = 8
 // shard of the metric config); a.variant 1 forces k_rollout, 2 k_rollout_v. k_rollout_v steps the
-// synthetic cheetah only: a Pendulum or CartPole env never takes it.
+// synthetic cheetah only: a Pendulum, CartPole or Reacher env never takes it.
 static bool use_rollout_v(const RolloutArgs& a) {
   if (a.env.kind != PSYN_CHEETAH) return false;
   if (a.K.kind != PPO_NET_LN_BETA || a.K.OP > 32 || a.env.w.on || !a.s_beta || a.variant == 1) return false;
@@ -1614,6 +1725,12 @@ int launch_rollout(const RolloutArgs& a, hipStream_t s) {
     if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<1, 1, PSYN_CARTPOLE>(a, s);
     if (a.env.w.on) return -1;
     return launch_rollout_t<1, 1, PSYN_CARTPOLE>(a, s);
+  }
+  if (a.env.kind == PSYN_REACHER) {  // O = 10, A = 2: one input tile, one head tile
+    if (a.K.OP != 16 || a.K.A != REACH_ACT_DIM) return -1;
+    if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<1, 1, PSYN_REACHER>(a, s);
+    if (a.env.w.on) return -1;
+    return launch_rollout_t<1, 1, PSYN_REACHER>(a, s);
   }
   if (a.env.kind != PSYN_CHEETAH) return -1;
   if (use_rollout_v(a)) return a.K.OP == 16 ? launch_rollout_v_t<1>(a, s) : launch_rollout_v_t<2>(a, s);

@@ -191,13 +191,19 @@ def parser():
     ap.add_argument("--adam_eps", type=float, default=1e-5)
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "pendulum", "learning_ref.json"))
     ap.add_argument("--curve", action="store_true")
+    ap.add_argument("--jobs", type=int, default=1, help="seeds run in this many processes (the results do not change)")
     return ap
 
 
 def main(a=None, env_id=ENV, dims=(OD, AD), host=HostPendulum):
     a = a or parser().parse_args()
     t0 = time.time()
-    runs = [run_seed(a, s, a.curve, env_id=env_id, dims=dims, host=host) for s in a.seeds]
+    if getattr(a, "jobs", 1) > 1:  # one forked process per seed, before any library is loaded
+        import multiprocessing as mp
+        with mp.get_context("fork").Pool(min(a.jobs, len(a.seeds))) as pool:
+            runs = pool.starmap(run_seed, [(a, s, a.curve, None, False, env_id, dims, host) for s in a.seeds])
+    else:
+        runs = [run_seed(a, s, a.curve, env_id=env_id, dims=dims, host=host) for s in a.seeds]
     un = [r["untrained"] for r in runs]
     spread = max(un) - min(un)
     imp = [r["trained"] - r["untrained"] for r in runs]
