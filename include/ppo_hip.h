@@ -81,7 +81,7 @@ int ppo_runtime_check(void);
 /* The AC agent's fixed observation normalisation for env_id (AgentImpl mean_ / std_; reference
  * ac_ppo_continuous_action.cpp Humanoid-v4 :496-497, Ant-v5 :521-522, Hopper-v5 :533-534).
  * HalfCheetah-v5 uses zeros / ones (:510-511): returns 0 with *n = 0; so does
- * CartPoleContinuous-v1 (raw observations) and ReacherPlanar-v0. Unknown env id: error.
+ * CartPoleContinuous-v1 (raw observations), ReacherPlanar-v0 and QuadrotorHover-v0. Unknown env id: error.
  * The arrays are static (owned by the library). */
 int ppo_obs_norm(const char* env_id, const float** mean, const float** std, int* n);
 

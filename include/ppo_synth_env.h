@@ -38,6 +38,16 @@
  * touches: it survives every step and is redrawn at every autoreset. The dynamics clip both actions to
  * [-1, 1] themselves; the termination flag passed to the wrapper chain is always 0. Not covered for
  * this kind: the VALU rollout kernel (rollout_kernel=valu is refused).
+ *
+ * A fifth kind, PSYN_QUADROTOR (psyn_create_env("QuadrotorHover-v0")), is the first real task wider
+ * than one 16-wide input tile: a rigid-body quadrotor hovering at the origin, O = 18, A = 4, action
+ * space [-1, 1] per dimension, termination when |p|^2 > 9, truncation after 500 steps. It is this
+ * project's own task over the textbook Newton-Euler equations, not a simulator's quadrotor, with the
+ * arithmetic of include/ppo_quadrotor.h — bit for bit the host env ppo.cpp_amd/gymcpp/quadrotor.h.
+ * Its state q [E, 18] holds p, v, the unit quaternion (w, x, y, z), omega and five unused slots. The
+ * dynamics clip the four actions to [-1, 1] themselves; the termination flag reaches the wrapper
+ * chain as CartPole's does. Not covered for this kind: the VALU rollout kernel (rollout_kernel=valu
+ * is refused).
  */
 #ifndef PPO_SYNTH_ENV_H
 #define PPO_SYNTH_ENV_H
@@ -50,10 +60,11 @@ typedef struct psyn_env psyn_t;
 
 int psyn_create(int num_envs, int obs_dim, int act_dim, psyn_t** out);
 /* The env kinds. psyn_create gives PSYN_CHEETAH at any (obs_dim, act_dim). */
-enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1, PSYN_CARTPOLE = 2, PSYN_REACHER = 3 };
+enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1, PSYN_CARTPOLE = 2, PSYN_REACHER = 3, PSYN_QUADROTOR = 4 };
 /* By env id: "Pendulum-v1" (PSYN_PENDULUM: O = 3, A = 1, action space [-2, 2]),
  * "CartPoleContinuous-v1" (PSYN_CARTPOLE: O = 4, A = 1, action space [-1, 1]),
- * "ReacherPlanar-v0" (PSYN_REACHER: O = 10, A = 2, action space [-1, 1]^2) or
+ * "ReacherPlanar-v0" (PSYN_REACHER: O = 10, A = 2, action space [-1, 1]^2),
+ * "QuadrotorHover-v0" (PSYN_QUADROTOR: O = 18, A = 4, action space [-1, 1]^4) or
  * "SyntheticCheetah-v0" (the env of psyn_create(num_envs, 17, 6)). Any other id, a NULL argument or
  * num_envs <= 0 is refused (-1, ppo_last_error lists the ids) before any HIP call. */
 int psyn_create_env(const char* env_id, int num_envs, psyn_t** out);

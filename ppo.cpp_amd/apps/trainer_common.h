@@ -36,6 +36,7 @@
 #include "../gymcpp/pendulum.h"
 #include "../gymcpp/cartpole.h"
 #include "../gymcpp/reacher.h"
+#include "../gymcpp/quadrotor.h"
 #include "tensorboard_logger.h"
 #include "../gymcpp/wrappers.h"
 
@@ -357,10 +358,11 @@ struct EnvSpec {
 // Shape of the device env (--env_backend device) for an env id: the synthetic dynamics of
 // include/ppo_synth_env.h at the observation / action widths and action bounds of the reference's
 // MuJoCo env (libs/gymcpp/mujoco/half_cheetah_v5.h:31-34, humanoid_v4.h:27-30, ant_v5.h:38-41,
-// hopper_v5.h:35-38). Pendulum-v1, CartPoleContinuous-v1 and ReacherPlanar-v0 are the ids with dynamics
-// of their own on the device (PSYN_PENDULUM, Gymnasium's pendulum.py; PSYN_CARTPOLE, Gymnasium's
-// cartpole.py with a continuous force; PSYN_REACHER, Reacher-v5's task definition over the textbook
-// two-link arm, not MuJoCo's Reacher). Returns false for an unknown id.
+// hopper_v5.h:35-38). Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0 and QuadrotorHover-v0 are the
+// ids with dynamics of their own on the device (PSYN_PENDULUM, Gymnasium's pendulum.py; PSYN_CARTPOLE,
+// Gymnasium's cartpole.py with a continuous force; PSYN_REACHER, Reacher-v5's task definition over the
+// textbook two-link arm, not MuJoCo's Reacher; PSYN_QUADROTOR, the project's own hover task over the
+// textbook Newton-Euler quadrotor). Returns false for an unknown id.
 struct EnvShape {
   int O, A;
   float lo, hi;
@@ -373,17 +375,19 @@ inline bool device_env_shape(const std::string& env_id, EnvShape* s) {
   else if (env_id == "Pendulum-v1") *s = {PEND_OBS_DIM, PEND_ACT_DIM, -PEND_MAX_TORQUE, PEND_MAX_TORQUE};
   else if (env_id == "CartPoleContinuous-v1") *s = {CART_OBS_DIM, CART_ACT_DIM, -1.0f, 1.0f};
   else if (env_id == "ReacherPlanar-v0") *s = {REACH_OBS_DIM, REACH_ACT_DIM, -1.0f, 1.0f};
+  else if (env_id == "QuadrotorHover-v0") *s = {QUAD_OBS_DIM, QUAD_ACT_DIM, -1.0f, 1.0f};
   else return false;
   return true;
 }
 inline const char* device_env_ids() {
   return "HalfCheetah-v5, Humanoid-v4, Ant-v5, Hopper-v5, SyntheticCheetah-v0, Pendulum-v1, CartPoleContinuous-v1, "
-         "ReacherPlanar-v0";
+         "ReacherPlanar-v0, QuadrotorHover-v0";
 }
-// the device env of an env id: Pendulum-v1, CartPoleContinuous-v1 and ReacherPlanar-v0 by id (kinds of
-// their own), every other id the synthetic dynamics at the id's shape
+// the device env of an env id: Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0 and QuadrotorHover-v0
+// by id (kinds of their own), every other id the synthetic dynamics at the id's shape
 inline int create_device_env(const std::string& env_id, int E, const EnvShape& sh, psyn_t** out) {
-  if (env_id == "Pendulum-v1" || env_id == "CartPoleContinuous-v1" || env_id == "ReacherPlanar-v0")
+  if (env_id == "Pendulum-v1" || env_id == "CartPoleContinuous-v1" || env_id == "ReacherPlanar-v0" ||
+      env_id == "QuadrotorHover-v0")
     return psyn_create_env(env_id.c_str(), E, out);
   return psyn_create(E, sh.O, sh.A, out);
 }
@@ -394,12 +398,14 @@ inline std::shared_ptr<gymcpp::Environment> make_base_env(const std::string& env
   if (env_id == "Pendulum-v1") return std::make_shared<gymcpp::Pendulum>();
   if (env_id == "CartPoleContinuous-v1") return std::make_shared<gymcpp::CartPoleContinuous>();
   if (env_id == "ReacherPlanar-v0") return std::make_shared<gymcpp::ReacherPlanar>();
+  if (env_id == "QuadrotorHover-v0") return std::make_shared<gymcpp::QuadrotorHover>();
   if (env_id == "Humanoid-v4" || env_id == "HalfCheetah-v5" || env_id == "Ant-v5" || env_id == "Hopper-v5")
     throw std::invalid_argument("env_id: " + env_id +
                                 " needs MuJoCo 3.2.0, which this build does not link; use SyntheticCheetah-v0, "
-                                "Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0 or the device env (--env_backend device)");
+                                "Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0 or the device env "
+                                "(--env_backend device)");
   throw std::invalid_argument("env_id: " + env_id + " is not implemented (host envs: SyntheticCheetah-v0, Pendulum-v1, "
-                              "CartPoleContinuous-v1, ReacherPlanar-v0).");
+                              "CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0).");
 }
 
 // Host threads this process may use: the launcher's thread budget (OMP_NUM_THREADS, set to the box's

@@ -29,6 +29,7 @@
 #include "../../include/ppo_pendulum.h"
 #include "../../include/ppo_cartpole.h"
 #include "../../include/ppo_reacher.h"
+#include "../../include/ppo_quadrotor.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -111,6 +112,7 @@ extern "C" int ppo_obs_norm(const char* env_id, const float** mean, const float*
   if (!strcmp(env_id, "HalfCheetah-v5")) return 0;  // zeros / ones (ac:510-511): identity
   if (!strcmp(env_id, "CartPoleContinuous-v1")) return 0;  // raw (x, xdot, theta, thetadot): identity
   if (!strcmp(env_id, "ReacherPlanar-v0")) return 0;       // all ten values are of order 1 or smaller: identity
+  if (!strcmp(env_id, "QuadrotorHover-v0")) return 0;      // positions, a rotation matrix, speeds of order 1: identity
   for (const ObsNormEntry& e : k_obs_norm)
     if (!strcmp(env_id, e.env_id)) {
       *mean = e.mean;
@@ -1705,9 +1707,17 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
     HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * REACH_OBS_DIM));
     return 0;
   }
+  if (id == "QuadrotorHover-v0") {
+    if (int rc = psyn_create(E, QUAD_OBS_DIM, QUAD_ACT_DIM, out)) return rc;
+    (*out)->a.kind = PSYN_QUADROTOR;  // action space [-1, 1]: psyn_create's default
+    // q [E, 18] holds p, v, the quaternion and omega; the five unused slots are defined from the start
+    // (the persistent kernels carry them along)
+    HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * QUAD_OBS_DIM));
+    return 0;
+  }
   if (id != "Pendulum-v1")
     return fail("psyn_create_env: unknown env_id " + id +
-                " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1, ReacherPlanar-v0");
+                " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0");
   if (int rc = psyn_create(E, PEND_OBS_DIM, PEND_ACT_DIM, out)) return rc;
   (*out)->a.kind = PSYN_PENDULUM;
   (*out)->act_lo = -PEND_MAX_TORQUE;
@@ -1721,12 +1731,14 @@ static int psyn_max_steps(const psyn_t* env) {
   return env->a.kind == PSYN_PENDULUM   ? PEND_MAX_STEPS
          : env->a.kind == PSYN_CARTPOLE ? CART_MAX_STEPS
          : env->a.kind == PSYN_REACHER  ? REACH_MAX_STEPS
+         : env->a.kind == PSYN_QUADROTOR ? QUAD_MAX_STEPS
                                         : 1000;
 }
 static const char* psyn_kind_name(int kind) {
   return kind == PSYN_PENDULUM ? "PSYN_PENDULUM (Pendulum-v1)"
          : kind == PSYN_CARTPOLE ? "PSYN_CARTPOLE (CartPoleContinuous-v1)"
          : kind == PSYN_REACHER  ? "PSYN_REACHER (ReacherPlanar-v0)"
+         : kind == PSYN_QUADROTOR ? "PSYN_QUADROTOR (QuadrotorHover-v0)"
                                  : "PSYN_CHEETAH";
 }
 
@@ -1859,13 +1871,14 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
   if (cfg->chunk_steps < 0 || (cfg->mode != 0 && cfg->mode != 1)) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
   // an env that terminates can finish an episode every other step, so its chunks are shorter by
   // default (the event buffer below is sized for the worst case)
-  const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : (env->a.kind == PSYN_CARTPOLE ? 512 : 4096);
+  const bool terminates = env->a.kind == PSYN_CARTPOLE || env->a.kind == PSYN_QUADROTOR;
+  const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : (terminates ? 512 : 4096);
   const bool persistent = cfg->mode == 0 && eval_supported(c->K) == 0 && !env->a.w.on;
   // the env truncates after max_steps (1000; Pendulum 200) steps and resets on the next one: an env
   // finishes at most one episode per max_steps + 1 steps, which bounds the events of a chunk (an
-  // overflow is still detected). CartPoleContinuous-v1 terminates: an episode is at least one step
-  // and the reset step after it, so an env finishes at most one episode per 2 steps.
-  const int min_period = env->a.kind == PSYN_CARTPOLE ? 2 : psyn_max_steps(env) + 1;
+  // overflow is still detected). CartPoleContinuous-v1 and QuadrotorHover-v0 terminate: an episode is
+  // at least one step and the reset step after it, so an env finishes at most one episode per 2 steps.
+  const int min_period = terminates ? 2 : psyn_max_steps(env) + 1;
   const long devcap = (long)nE * (chunk / min_period + 2);
   hipStream_t s = c->stream;
   struct Scratch {

@@ -15,12 +15,12 @@
 #include "ppo_pendulum_dev.hpp"
 #include "ppo_cartpole_dev.hpp"
 #include "ppo_reacher_dev.hpp"
+#include "ppo_quadrotor_dev.hpp"
 
 // KIND: the device env's kind, compile-time as in k_rollout
 template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
-  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1),
-                "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1; ReacherPlanar-v0: O = 10, A = 2");
+  static_assert(psyn_kind_tiles_ok(KIND, NTO, NHT), PSYN_KIND_TILES_MSG);
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -253,6 +253,46 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
 #pragma unroll
         for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = o10[i];
       }
+    } else if constexpr (KIND == PSYN_QUADROTOR) {
+      // QuadrotorHover-v0 (k_quad_step arithmetic): lane 0 of each env's lane group steps the env
+      // from its four actions, ACT[r * 24 + 0..3], in place on the env's LDS rows (state in Q,
+      // observation into XO); an episode that terminates or is truncated is one event
+#pragma clang fp contract(off)
+      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          quad_reset_dev(rc, rs, q);
+          quad_obs(q, xo);
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EVI[EV_AR * R + r] = 0;
+        } else {
+          const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi),
+                                          fminf(fmaxf(ACT[r * 24 + 2], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 3], a.lo), a.hi)};
+          float te;
+          const float rw = quad_step(q, ac, xo, &te);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool fin = (te != 0.0f) || tt >= QUAD_MAX_STEPS;  // done = terminated or truncated
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (fin) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+            const unsigned slot = atomicAdd(a.count, 1u);
+            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
+          }
+          EVI[EV_AR * R + r] = fin ? 1 : 0;
+        }
+      }
     } else {
       // the synthetic cheetah (k_synth_step arithmetic)
 #pragma clang fp contract(off)
@@ -390,6 +430,8 @@ int launch_eval(const EvalArgs& a, hipStream_t s) {
   if (a.env.kind == PSYN_CARTPOLE) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_CARTPOLE>(a, s) : -1;
   if (a.env.kind == PSYN_REACHER)
     return (a.K.OP == 16 && a.K.A == REACH_ACT_DIM) ? launch_eval_t<1, PSYN_REACHER>(a, s) : -1;
+  if (a.env.kind == PSYN_QUADROTOR)
+    return (a.K.OP == 32 && a.K.A == QUAD_ACT_DIM) ? launch_eval_t<2, PSYN_QUADROTOR>(a, s) : -1;
   if (a.env.kind != PSYN_CHEETAH) return -1;
   return a.K.OP == 16 ? launch_eval_t<1>(a, s) : launch_eval_t<2>(a, s);
 }

@@ -16,12 +16,14 @@
 //   k_pend_*     Pendulum-v1 device env, per-step form (the fused form is in ppo_rollout.hip / ppo_eval.hip)
 //   k_cart_*     CartPoleContinuous-v1 device env (it terminates), per-step form (fused form: as k_pend_*)
 //   k_reach_*    ReacherPlanar-v0 device env (O = 10, A = 2, a goal per episode), per-step form (fused form: as k_pend_*)
+//   k_quad_*     QuadrotorHover-v0 device env (O = 18, A = 4, it terminates), per-step form (fused form: as k_pend_*)
 #include "ppo_agent.hpp"
 #include "ppo_kernels.hpp"
 #include "ppo_wrap.hpp"
 #include "ppo_pendulum_dev.hpp"
 #include "ppo_cartpole_dev.hpp"
 #include "ppo_reacher_dev.hpp"
+#include "ppo_quadrotor_dev.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2661,6 +2663,85 @@ __global__ __launch_bounds__(256) void k_reach_step(SynthArgs a, int e0, int e1,
   a.autoreset[e] = tr ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PSYN_QUADROTOR (QuadrotorHover-v0, O = 18, A = 4): one lane per env, the bookkeeping of
+// k_cart_step: the episodes terminate (|p|^2 > 9) and truncate (500 steps), the termination flag
+// goes to wrap_reward. The state q[0..12] = (p, v, quaternion, omega). The step reads all four
+// actions of the env. The dynamics are include/ppo_quadrotor.h, bit for bit gymcpp/quadrotor.h.
+// ---------------------------------------------------------------------------------------------
+PPO_DEV void quad_store_obs(const SynthArgs& a, int e, float oc, const float* o18, float* obs) {
+  for (int i = 0; i < QUAD_OBS_DIM; ++i)
+    obs[(long)e * QUAD_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, QUAD_OBS_DIM, i, oc, o18[i]) : o18[i];
+  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
+}
+
+__global__ __launch_bounds__(256) void k_quad_reset(SynthArgs a, int seed, float* obs, float* done) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
+  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+  float s13[QUAD_STATE_DIM], o18[QUAD_OBS_DIM];
+  quad_reset_dev(rc, rs, s13);
+  quad_obs(s13, o18);
+  float* q = a.q + (long)e * QUAD_OBS_DIM;
+  for (int i = 0; i < QUAD_STATE_DIM; ++i) q[i] = s13[i];
+  quad_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o18, obs);
+  a.rcount[e] = rc + 1;
+  a.t[e] = 0;
+  a.ep_ret[e] = 0.0f;
+  a.ep_len[e] = 0;
+  a.autoreset[e] = 0;
+  if (done) done[e] = 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_quad_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
+                                                   float lo, float hi, float* __restrict__ obs,
+                                                   float* __restrict__ reward, float* __restrict__ done) {
+#pragma clang fp contract(off)
+  const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= e1) return;
+  float* __restrict__ q = a.q + (long)e * QUAD_OBS_DIM;
+  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
+  float s13[QUAD_STATE_DIM], o18[QUAD_OBS_DIM];
+  if (a.autoreset[e] != 0) {
+    const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+    quad_reset_dev(rc, rs, s13);
+    quad_obs(s13, o18);
+    for (int i = 0; i < QUAD_STATE_DIM; ++i) q[i] = s13[i];
+    quad_store_obs(a, e, oc, o18, obs);
+    a.rcount[e] = rc + 1;
+    a.t[e] = 0;
+    a.ep_ret[e] = 0.0f;
+    a.ep_len[e] = 0;
+    reward[e] = 0.0f;
+    done[e] = 0.0f;
+    a.autoreset[e] = 0;
+    return;
+  }
+  for (int i = 0; i < QUAD_STATE_DIM; ++i) s13[i] = q[i];
+  const float* __restrict__ ar = act + (long)(e - e0) * QUAD_ACT_DIM;
+  // clip_actions, per dimension; the dynamics clip to +-1 themselves
+  const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ar[0], lo), hi), fminf(fmaxf(ar[1], lo), hi),
+                                  fminf(fmaxf(ar[2], lo), hi), fminf(fmaxf(ar[3], lo), hi)};
+  float te;
+  const float r = quad_step(s13, ac, o18, &te);
+  for (int i = 0; i < QUAD_STATE_DIM; ++i) q[i] = s13[i];
+  quad_store_obs(a, e, oc, o18, obs);
+  const int t = a.t[e] + 1;
+  a.t[e] = t;
+  const bool fin = (te != 0.0f) || t >= QUAD_MAX_STEPS;  // done = terminated or truncated
+  reward[e] = a.w.on ? wrap_reward(a.w, e, r, te) : r;
+  done[e] = fin ? 1.0f : 0.0f;
+  a.ep_ret[e] = (a.ep_ret[e] + r);
+  a.ep_len[e] += 1;
+  if (fin) {
+    a.fin_ret[e] += a.ep_ret[e];
+    a.fin_len[e] += (float)a.ep_len[e];
+    a.fin_cnt[e] += 1.0f;
+  }
+  a.autoreset[e] = fin ? 1 : 0;
+}
+
 // =============================================================================================
 // explicit instantiations / launch wrappers
 // =============================================================================================
@@ -2912,6 +2993,10 @@ void launch_synth_reset(const SynthArgs& a, int seed, float* obs, float* done, h
     hipLaunchKernelGGL(k_reach_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
     return;
   }
+  if (a.kind == PSYN_QUADROTOR) {
+    hipLaunchKernelGGL(k_quad_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
+    return;
+  }
   hipLaunchKernelGGL(k_synth_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
 }
 void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, float lo, float hi, float* obs,
@@ -2928,6 +3013,11 @@ void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, flo
   }
   if (a.kind == PSYN_REACHER) {
     hipLaunchKernelGGL(k_reach_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
+                       done);
+    return;
+  }
+  if (a.kind == PSYN_QUADROTOR) {
+    hipLaunchKernelGGL(k_quad_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
                        done);
     return;
   }

@@ -259,9 +259,10 @@ struct WrapArgs {
 struct SynthArgs {
   WrapArgs w;  // applied inside the env's own kernels when w.on
   int E, O, A;
-  int kind;    // PSYN_CHEETAH | PSYN_PENDULUM | PSYN_CARTPOLE | PSYN_REACHER (include/ppo_synth_env.h)
+  int kind;    // PSYN_CHEETAH | PSYN_PENDULUM | PSYN_CARTPOLE | PSYN_REACHER | PSYN_QUADROTOR (include/ppo_synth_env.h)
   float* q;    // [E][O] env state; Pendulum: theta, thetadot, one unused slot; CartPole: x, xdot, theta, thetadot;
-               // Reacher: q1, q2, q1dot, q2dot, gx, gy, four unused slots
+               // Reacher: q1, q2, q1dot, q2dot, gx, gy, four unused slots; Quadrotor: p, v, quaternion, omega,
+               // five unused slots
   int* t;
   int* autoreset;
   uint32_t* rseed;

@@ -22,6 +22,7 @@
 #include "ppo_pendulum_dev.hpp"
 #include "ppo_cartpole_dev.hpp"
 #include "ppo_reacher_dev.hpp"
+#include "ppo_quadrotor_dev.hpp"
 
 #include <type_traits>
 
@@ -61,13 +62,13 @@ constexpr int kRdbgEnv = 26;
 // =============================================================================================
 // k_rollout: T steps of {actor act + sample, synthetic env step} for 16 envs per workgroup
 // =============================================================================================
-// KIND: the device env's kind (PSYN_CHEETAH | PSYN_PENDULUM | PSYN_CARTPOLE | PSYN_REACHER), a
-// compile-time parameter so that the cheetah instantiations carry nothing of the Pendulum, CartPole
-// or Reacher step (and compile to the code they had)
+// KIND: the device env's kind (PSYN_CHEETAH | PSYN_PENDULUM | PSYN_CARTPOLE | PSYN_REACHER |
+// PSYN_QUADROTOR), a compile-time parameter so that the cheetah instantiations carry nothing of the
+// Pendulum, CartPole, Reacher or Quadrotor step (and compile to the code they had). The kind is
+// independent of the tile count: psyn_kind_tiles_ok names the shapes each kind is built at.
 template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
-  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1),
-                "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1; ReacherPlanar-v0: O = 10, A = 2");
+  static_assert(psyn_kind_tiles_ok(KIND, NTO, NHT), PSYN_KIND_TILES_MSG);
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -359,6 +360,49 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
 #pragma unroll
         for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = o10[i];
       }
+    } else if constexpr (KIND == PSYN_QUADROTOR) {
+      // QuadrotorHover-v0 (k_quad_step arithmetic): lane 0 of each env's lane group steps the env
+      // from its four actions, ACT[r * 24 + 0..3] (written by other lanes before the barrier above).
+      // The step works on the env's LDS rows in place (state in Q, observation into XO) instead of
+      // carrying 13 + 18 values in registers next to the resident weights.
+#pragma clang fp contract(off)
+      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          quad_reset_dev(rc, rs, q);
+          quad_obs(q, xo);
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EV[EV_DONE * R + r] = 0.0f;
+          EVI[EV_AR * R + r] = 0;
+          a.s_rewards[(long)t * E + e] = 0.0f;
+        } else {
+          const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi),
+                                          fminf(fmaxf(ACT[r * 24 + 2], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 3], a.lo), a.hi)};
+          float te;
+          const float rw = quad_step(q, ac, xo, &te);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool fin = (te != 0.0f) || tt >= QUAD_MAX_STEPS;  // done = terminated or truncated
+          a.s_rewards[(long)t * E + e] = rw;  // (no wrapper chain in this kernel: te feeds done only)
+          EV[EV_DONE * R + r] = fin ? 1.0f : 0.0f;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (fin) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+          }
+          EVI[EV_AR * R + r] = fin ? 1 : 0;
+        }
+      }
     } else {
       // the synthetic cheetah (k_synth_step / k_synth_step_wide arithmetic)
 #pragma clang fp contract(off)
@@ -639,8 +683,7 @@ PPO_DEV f4 trunk4(const f4 (&xv)[NKW], const f4 (&wa)[NKW][4], const f4 (&w2v)[4
 // the VALU-bound wrapper chain a quarter.
 template <int NTO, int NHT, int RR, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
-  static_assert(KIND == PSYN_CHEETAH || (NTO == 1 && NHT == 1),
-                "Pendulum-v1: O = 3, A = 1; CartPoleContinuous-v1: O = 4, A = 1; ReacherPlanar-v0: O = 10, A = 2");
+  static_assert(psyn_kind_tiles_ok(KIND, NTO, NHT), PSYN_KIND_TILES_MSG);
   constexpr int H = kR4H, R = RR, OP = NTO * 16, NKW = (NTO + 3) / 4, NHP = NHT * 16;
   constexpr int LPE = kR4Threads / RR;  // env lanes per env (one env within one wave)
   constexpr int LDQ = Roll4Geo<NTO, NHT>::LDQ, NCE = (OP + LPE - 1) / LPE, kEnvGroup = 12;
@@ -969,6 +1012,60 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
 #pragma unroll
         for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, o10[i]) : o10[i];
         if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
+      }
+    } else if constexpr (KIND == PSYN_QUADROTOR) {
+      // QuadrotorHover-v0 (k_quad_step arithmetic): lane 0 of each env's lane group steps the env
+      // from its four actions, ACT[r * 32 + 0..3] (written by other lanes before the barrier above).
+      // The step's termination flag te goes to NormalizeReward; an episode ends on termination or
+      // truncation, on any step, env by env. The step works on the env's LDS rows in place: the state
+      // in Q, the raw observation into XO, which the wrapper chain then normalises where it lies.
+#pragma clang fp contract(off)
+      const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
+      if (i0 == 0 && e < E) {
+        float* q = Q + r * LDQ;
+        float* xo = XO + r * LDQ;
+        float* om = WOM + r * LDQ;
+        float* ov = WOV + r * LDQ;
+        const float oc = EV[EV_WOC * R + r];
+        if (EVI[EV_AR * R + r] != 0) {
+          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+          quad_reset_dev(rc, rs, q);
+          quad_obs(q, xo);
+          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+          EVI[EV_T * R + r] = 0;
+          EV[EV_EPR * R + r] = 0.0f;
+          EVI[EV_EPL * R + r] = 0;
+          EV[EV_DONE * R + r] = 0.0f;
+          EVI[EV_AR * R + r] = 0;
+          a.s_rewards[(long)t * E + e] = 0.0f;
+        } else {
+          const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ACT[r * 32 + 0], a.lo), a.hi), fminf(fmaxf(ACT[r * 32 + 1], a.lo), a.hi),
+                                          fminf(fmaxf(ACT[r * 32 + 2], a.lo), a.hi), fminf(fmaxf(ACT[r * 32 + 3], a.lo), a.hi)};
+          float te;
+          const float rw = quad_step(q, ac, xo, &te);
+          const int tt = EVI[EV_T * R + r] + 1;
+          EVI[EV_T * R + r] = tt;
+          const bool fin = (te != 0.0f) || tt >= QUAD_MAX_STEPS;  // done = terminated or truncated
+          a.s_rewards[(long)t * E + e] =
+              w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
+                                    EV + EV_WRC * R + r, w.gamma, rw, te)
+                   : rw;
+          EV[EV_DONE * R + r] = fin ? 1.0f : 0.0f;
+          const float epr = (EV[EV_EPR * R + r] + rw);
+          EV[EV_EPR * R + r] = epr;
+          const int epl = EVI[EV_EPL * R + r] + 1;
+          EVI[EV_EPL * R + r] = epl;
+          if (fin) {
+            EV[EV_FR * R + r] += epr;
+            EV[EV_FL * R + r] += (float)epl;
+            EV[EV_FC * R + r] += 1.0f;
+          }
+          EVI[EV_AR * R + r] = fin ? 1 : 0;
+        }
+        if (w.on) {
+          for (int i = 0; i < QUAD_OBS_DIM; ++i) xo[i] = wrap_obs_at(om + i, ov + i, oc, xo[i]);
+          EV[EV_WOC * R + r] = oc + 1.0f;
+        }
       }
     } else {
       // the synthetic cheetah (k_synth_step / _wide arithmetic)
@@ -1702,7 +1799,7 @@ static int launch_rollout_v_t(const RolloutArgs& a, hipStream_t s) {
 
 // the VALU rollout where it applies: AC agent, O <= 32, and few envs (auto: E <= 512, the N = 8
 // shard of the metric config); a.variant 1 forces k_rollout, 2 k_rollout_v. k_rollout_v steps the
-// synthetic cheetah only: a Pendulum, CartPole or Reacher env never takes it.
+// synthetic cheetah only: a Pendulum, CartPole, Reacher or Quadrotor env never takes it.
 static bool use_rollout_v(const RolloutArgs& a) {
   if (a.env.kind != PSYN_CHEETAH) return false;
   if (a.K.kind != PPO_NET_LN_BETA || a.K.OP > 32 || a.env.w.on || !a.s_beta || a.variant == 1) return false;
@@ -1731,6 +1828,12 @@ int launch_rollout(const RolloutArgs& a, hipStream_t s) {
     if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<1, 1, PSYN_REACHER>(a, s);
     if (a.env.w.on) return -1;
     return launch_rollout_t<1, 1, PSYN_REACHER>(a, s);
+  }
+  if (a.env.kind == PSYN_QUADROTOR) {  // O = 18, A = 4: two input tiles, one head tile
+    if (a.K.OP != 32 || a.K.A != QUAD_ACT_DIM) return -1;
+    if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<2, 1, PSYN_QUADROTOR>(a, s);
+    if (a.env.w.on) return -1;
+    return launch_rollout_t<2, 1, PSYN_QUADROTOR>(a, s);
   }
   if (a.env.kind != PSYN_CHEETAH) return -1;
   if (use_rollout_v(a)) return a.K.OP == 16 ? launch_rollout_v_t<1>(a, s) : launch_rollout_v_t<2>(a, s);
