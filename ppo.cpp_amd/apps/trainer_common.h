@@ -355,57 +355,80 @@ struct EnvSpec {
   float act_min = -1, act_max = 1;
 };
 
-// Shape of the device env (--env_backend device) for an env id: the synthetic dynamics of
-// include/ppo_synth_env.h at the observation / action widths and action bounds of the reference's
-// MuJoCo env (libs/gymcpp/mujoco/half_cheetah_v5.h:31-34, humanoid_v4.h:27-30, ant_v5.h:38-41,
-// hopper_v5.h:35-38). Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0 and QuadrotorHover-v0 are the
-// ids with dynamics of their own on the device (PSYN_PENDULUM, Gymnasium's pendulum.py; PSYN_CARTPOLE,
-// Gymnasium's cartpole.py with a continuous force; PSYN_REACHER, Reacher-v5's task definition over the
-// textbook two-link arm, not MuJoCo's Reacher; PSYN_QUADROTOR, the project's own hover task over the
-// textbook Newton-Euler quadrotor). Returns false for an unknown id.
+// The env ids of the trainers, one list. shape: the device env (--env_backend device) of the id.
+// own_kind ids have dynamics of their own on the device and are created by id (psyn_create_env:
+// Pendulum-v1, Gymnasium's pendulum.py; CartPoleContinuous-v1, Gymnasium's cartpole.py with a continuous
+// force; ReacherPlanar-v0, Reacher-v5's task definition over the textbook two-link arm, not MuJoCo's
+// Reacher; QuadrotorHover-v0, the project's own hover task over the textbook Newton-Euler quadrotor).
+// Every other id runs the synthetic dynamics of include/ppo_synth_env.h at the observation / action
+// widths and action bounds of the reference's MuJoCo env (libs/gymcpp/mujoco/half_cheetah_v5.h:31-34,
+// humanoid_v4.h:27-30, ant_v5.h:38-41, hopper_v5.h:35-38). make_host: the host env; null for the
+// MuJoCo ids, which need libmujoco 3.2.0 (absent from this build).
 struct EnvShape {
   int O, A;
   float lo, hi;
 };
+struct EnvEntry {
+  const char* id;
+  EnvShape shape;
+  bool own_kind;
+  std::shared_ptr<gymcpp::Environment> (*make_host)();
+};
+template <typename Env>
+std::shared_ptr<gymcpp::Environment> make_host_env() { return std::make_shared<Env>(); }
+inline const std::vector<EnvEntry>& env_entries() {
+  static const std::vector<EnvEntry> k = {
+      {"HalfCheetah-v5", {17, 6, -1.0f, 1.0f}, false, nullptr},
+      {"Humanoid-v4", {376, 17, -0.4f, 0.4f}, false, nullptr},
+      {"Ant-v5", {105, 8, -1.0f, 1.0f}, false, nullptr},
+      {"Hopper-v5", {11, 3, -1.0f, 1.0f}, false, nullptr},
+      {"SyntheticCheetah-v0", {17, 6, -1.0f, 1.0f}, false, make_host_env<gymcpp::SyntheticCheetah>},
+      {"Pendulum-v1", {PEND_OBS_DIM, PEND_ACT_DIM, -PEND_MAX_TORQUE, PEND_MAX_TORQUE}, true, make_host_env<gymcpp::Pendulum>},
+      {"CartPoleContinuous-v1", {CART_OBS_DIM, CART_ACT_DIM, -1.0f, 1.0f}, true, make_host_env<gymcpp::CartPoleContinuous>},
+      {"ReacherPlanar-v0", {REACH_OBS_DIM, REACH_ACT_DIM, -1.0f, 1.0f}, true, make_host_env<gymcpp::ReacherPlanar>},
+      {"QuadrotorHover-v0", {QUAD_OBS_DIM, QUAD_ACT_DIM, -1.0f, 1.0f}, true, make_host_env<gymcpp::QuadrotorHover>},
+  };
+  return k;
+}
+inline const EnvEntry* find_env_entry(const std::string& env_id) {
+  for (const EnvEntry& e : env_entries())
+    if (env_id == e.id) return &e;
+  return nullptr;
+}
+// the listed ids, ", " between them; host_only: those with a host env
+inline std::string env_id_list(bool host_only) {
+  std::string s;
+  for (const EnvEntry& e : env_entries())
+    if (!host_only || e.make_host) s += (s.empty() ? "" : ", ") + std::string(e.id);
+  return s;
+}
+
+// Shape of the device env for an env id. Returns false for an unknown id.
 inline bool device_env_shape(const std::string& env_id, EnvShape* s) {
-  if (env_id == "HalfCheetah-v5" || env_id == "SyntheticCheetah-v0") *s = {17, 6, -1.0f, 1.0f};
-  else if (env_id == "Humanoid-v4") *s = {376, 17, -0.4f, 0.4f};
-  else if (env_id == "Ant-v5") *s = {105, 8, -1.0f, 1.0f};
-  else if (env_id == "Hopper-v5") *s = {11, 3, -1.0f, 1.0f};
-  else if (env_id == "Pendulum-v1") *s = {PEND_OBS_DIM, PEND_ACT_DIM, -PEND_MAX_TORQUE, PEND_MAX_TORQUE};
-  else if (env_id == "CartPoleContinuous-v1") *s = {CART_OBS_DIM, CART_ACT_DIM, -1.0f, 1.0f};
-  else if (env_id == "ReacherPlanar-v0") *s = {REACH_OBS_DIM, REACH_ACT_DIM, -1.0f, 1.0f};
-  else if (env_id == "QuadrotorHover-v0") *s = {QUAD_OBS_DIM, QUAD_ACT_DIM, -1.0f, 1.0f};
-  else return false;
-  return true;
+  const EnvEntry* e = find_env_entry(env_id);
+  if (e) *s = e->shape;
+  return e != nullptr;
 }
-inline const char* device_env_ids() {
-  return "HalfCheetah-v5, Humanoid-v4, Ant-v5, Hopper-v5, SyntheticCheetah-v0, Pendulum-v1, CartPoleContinuous-v1, "
-         "ReacherPlanar-v0, QuadrotorHover-v0";
+inline std::string device_env_ids() { return env_id_list(false); }
+inline bool is_device_env_id(const std::string& env_id) {
+  const EnvEntry* e = find_env_entry(env_id);
+  return e && e->own_kind;
 }
-// the device env of an env id: Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0 and QuadrotorHover-v0
-// by id (kinds of their own), every other id the synthetic dynamics at the id's shape
+// the device env of an env id: an id with a kind of its own by id, every other id the synthetic
+// dynamics at the id's shape
 inline int create_device_env(const std::string& env_id, int E, const EnvShape& sh, psyn_t** out) {
-  if (env_id == "Pendulum-v1" || env_id == "CartPoleContinuous-v1" || env_id == "ReacherPlanar-v0" ||
-      env_id == "QuadrotorHover-v0")
-    return psyn_create_env(env_id.c_str(), E, out);
+  if (is_device_env_id(env_id)) return psyn_create_env(env_id.c_str(), E, out);
   return psyn_create(E, sh.O, sh.A, out);
 }
 
-// creates one base env; MuJoCo envs need libmujoco 3.2.0 (absent from this build)
+// creates one base env
 inline std::shared_ptr<gymcpp::Environment> make_base_env(const std::string& env_id) {
-  if (env_id == "SyntheticCheetah-v0") return std::make_shared<gymcpp::SyntheticCheetah>();
-  if (env_id == "Pendulum-v1") return std::make_shared<gymcpp::Pendulum>();
-  if (env_id == "CartPoleContinuous-v1") return std::make_shared<gymcpp::CartPoleContinuous>();
-  if (env_id == "ReacherPlanar-v0") return std::make_shared<gymcpp::ReacherPlanar>();
-  if (env_id == "QuadrotorHover-v0") return std::make_shared<gymcpp::QuadrotorHover>();
-  if (env_id == "Humanoid-v4" || env_id == "HalfCheetah-v5" || env_id == "Ant-v5" || env_id == "Hopper-v5")
-    throw std::invalid_argument("env_id: " + env_id +
-                                " needs MuJoCo 3.2.0, which this build does not link; use SyntheticCheetah-v0, "
-                                "Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0 or the device env "
-                                "(--env_backend device)");
-  throw std::invalid_argument("env_id: " + env_id + " is not implemented (host envs: SyntheticCheetah-v0, Pendulum-v1, "
-                              "CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0).");
+  const EnvEntry* e = find_env_entry(env_id);
+  if (e && e->make_host) return e->make_host();
+  if (e)
+    throw std::invalid_argument("env_id: " + env_id + " needs MuJoCo 3.2.0, which this build does not link; use " +
+                                env_id_list(true) + " or the device env (--env_backend device)");
+  throw std::invalid_argument("env_id: " + env_id + " is not implemented (host envs: " + env_id_list(true) + ").");
 }
 
 // Host threads this process may use: the launcher's thread budget (OMP_NUM_THREADS, set to the box's

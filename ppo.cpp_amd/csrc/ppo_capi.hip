@@ -26,10 +26,7 @@
 #include "../../include/ppo_synth_env.h"
 #include "../../include/ppo_env_wrappers.h"
 #include "ppo_kernels.hpp"
-#include "../../include/ppo_pendulum.h"
-#include "../../include/ppo_cartpole.h"
-#include "../../include/ppo_reacher.h"
-#include "../../include/ppo_quadrotor.h"
+#include "ppo_env_kinds.hpp"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -1694,52 +1691,33 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
   if (E <= 0) return fail("psyn_create_env: num_envs must be positive");
   const std::string id = env_id;
   if (id == "SyntheticCheetah-v0") return psyn_create(E, 17, 6, out);
-  if (id == "CartPoleContinuous-v1") {
-    if (int rc = psyn_create(E, CART_OBS_DIM, CART_ACT_DIM, out)) return rc;
-    (*out)->a.kind = PSYN_CARTPOLE;  // action space [-1, 1]: psyn_create's default
-    return 0;
-  }
-  if (id == "ReacherPlanar-v0") {
-    if (int rc = psyn_create(E, REACH_OBS_DIM, REACH_ACT_DIM, out)) return rc;
-    (*out)->a.kind = PSYN_REACHER;  // action space [-1, 1]: psyn_create's default
-    // q [E, 10] holds q1, q2, q1dot, q2dot, gx, gy; the four unused slots are defined from the start
-    // (the persistent kernels carry them along)
-    HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * REACH_OBS_DIM));
-    return 0;
-  }
-  if (id == "QuadrotorHover-v0") {
-    if (int rc = psyn_create(E, QUAD_OBS_DIM, QUAD_ACT_DIM, out)) return rc;
-    (*out)->a.kind = PSYN_QUADROTOR;  // action space [-1, 1]: psyn_create's default
-    // q [E, 18] holds p, v, the quaternion and omega; the five unused slots are defined from the start
-    // (the persistent kernels carry them along)
-    HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * QUAD_OBS_DIM));
-    return 0;
-  }
-  if (id != "Pendulum-v1")
+  const EnvKindRow* row = nullptr;
+  for (const EnvKindRow& r : kEnvKinds)
+    if (id == r.env_id) row = &r;
+  if (!row)
     return fail("psyn_create_env: unknown env_id " + id +
                 " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0");
-  if (int rc = psyn_create(E, PEND_OBS_DIM, PEND_ACT_DIM, out)) return rc;
-  (*out)->a.kind = PSYN_PENDULUM;
-  (*out)->act_lo = -PEND_MAX_TORQUE;
-  (*out)->act_hi = PEND_MAX_TORQUE;
-  // the unused third state slot is defined from the start (the persistent kernels carry it along)
-  HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * PEND_OBS_DIM));
+  if (int rc = psyn_create(E, row->O, row->A, out)) return rc;
+  (*out)->a.kind = row->kind;
+  (*out)->act_lo = row->act_lo;
+  (*out)->act_hi = row->act_hi;
+  // the unused state slots of q [E, O] are defined from the start (the persistent kernels carry them along)
+  if (row->zero_q) HIP_TRY(hipMemset((*out)->a.q, 0, sizeof(float) * (size_t)E * row->O));
   return 0;
 }
 
+// the cheetah (no row in kEnvKinds) truncates after 1000 steps and never terminates
 static int psyn_max_steps(const psyn_t* env) {
-  return env->a.kind == PSYN_PENDULUM   ? PEND_MAX_STEPS
-         : env->a.kind == PSYN_CARTPOLE ? CART_MAX_STEPS
-         : env->a.kind == PSYN_REACHER  ? REACH_MAX_STEPS
-         : env->a.kind == PSYN_QUADROTOR ? QUAD_MAX_STEPS
-                                        : 1000;
+  const EnvKindRow* row = env_kind_row_of(env->a.kind);
+  return row ? row->max_steps : 1000;
 }
-static const char* psyn_kind_name(int kind) {
-  return kind == PSYN_PENDULUM ? "PSYN_PENDULUM (Pendulum-v1)"
-         : kind == PSYN_CARTPOLE ? "PSYN_CARTPOLE (CartPoleContinuous-v1)"
-         : kind == PSYN_REACHER  ? "PSYN_REACHER (ReacherPlanar-v0)"
-         : kind == PSYN_QUADROTOR ? "PSYN_QUADROTOR (QuadrotorHover-v0)"
-                                 : "PSYN_CHEETAH";
+static bool psyn_terminates(const psyn_t* env) {
+  const EnvKindRow* row = env_kind_row_of(env->a.kind);
+  return row && row->terminates;
+}
+static std::string psyn_kind_name(int kind) {
+  const EnvKindRow* row = env_kind_row_of(kind);
+  return row ? std::string(row->kind_name) + " (" + row->env_id + ")" : "PSYN_CHEETAH";
 }
 
 extern "C" int psyn_env_info(const psyn_t* env, int* kind, int* obs_dim, int* act_dim, int* max_steps) {
@@ -1871,7 +1849,7 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
   if (cfg->chunk_steps < 0 || (cfg->mode != 0 && cfg->mode != 1)) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
   // an env that terminates can finish an episode every other step, so its chunks are shorter by
   // default (the event buffer below is sized for the worst case)
-  const bool terminates = env->a.kind == PSYN_CARTPOLE || env->a.kind == PSYN_QUADROTOR;
+  const bool terminates = psyn_terminates(env);
   const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : (terminates ? 512 : 4096);
   const bool persistent = cfg->mode == 0 && eval_supported(c->K) == 0 && !env->a.w.on;
   // the env truncates after max_steps (1000; Pendulum 200) steps and resets on the next one: an env

@@ -12,15 +12,11 @@
 // Events go to a global buffer through a vector atomic counter, in any order; the host sorts them by
 // (step, env) (ppo_eval_events.hpp).
 #include "ppo_rollout_common.hpp"
-#include "ppo_pendulum_dev.hpp"
-#include "ppo_cartpole_dev.hpp"
-#include "ppo_reacher_dev.hpp"
-#include "ppo_quadrotor_dev.hpp"
 
 // KIND: the device env's kind, compile-time as in k_rollout
 template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
-  static_assert(psyn_kind_tiles_ok(KIND, NTO, NHT), PSYN_KIND_TILES_MSG);
+  static_assert(psyn_kind_tiles_ok<KIND, NTO, NHT>(), PSYN_KIND_TILES_MSG);
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -119,178 +115,17 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
     }
     lds_barrier();
     // ---- env step: 32 lanes per env; a finished episode is one event ----
-    if constexpr (KIND == PSYN_PENDULUM) {
-      // Pendulum-v1 (k_pend_step arithmetic): lane 0 of each env's lane group steps the env
+    if constexpr (KIND != PSYN_CHEETAH) {
+      // a kind with a DevEnv (k_env_step arithmetic): lane 0 of each env's lane group steps the env
+      // from its actions ACT[r * 24 + 0..A-1]; an episode that terminates or is truncated, on whatever
+      // step, is one event
 #pragma clang fp contract(off)
       const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
       if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float th, thd, o3[PEND_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          pend_reset_dev(rc, rs, &th, &thd);
-          pend_obs(th, thd, o3);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EVI[EV_AR * R + r] = 0;
-        } else {
-          th = q[0];
-          thd = q[1];
-          const float rw = pend_step(&th, &thd, fminf(fmaxf(ACT[r * 24], a.lo), a.hi), o3);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= PEND_MAX_STEPS;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-            const unsigned slot = atomicAdd(a.count, 1u);
-            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
-        q[0] = th;
-        q[1] = thd;
-#pragma unroll
-        for (int i = 0; i < PEND_OBS_DIM; ++i) xo[i] = o3[i];
-      }
-    } else if constexpr (KIND == PSYN_CARTPOLE) {
-      // CartPoleContinuous-v1 (k_cart_step arithmetic): lane 0 of each env's lane group steps the
-      // env; an episode that terminates or is truncated, on whatever step, is one event
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float s4[CART_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          cart_reset_dev(rc, rs, s4);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EVI[EV_AR * R + r] = 0;
-        } else {
-#pragma unroll
-          for (int i = 0; i < CART_OBS_DIM; ++i) s4[i] = q[i];
-          float te;
-          const float rw = cart_step(s4, fminf(fmaxf(ACT[r * 24], a.lo), a.hi), &te);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool fin = (te != 0.0f) || tt >= CART_MAX_STEPS;  // done = terminated or truncated
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (fin) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-            const unsigned slot = atomicAdd(a.count, 1u);
-            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
-          }
-          EVI[EV_AR * R + r] = fin ? 1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < CART_OBS_DIM; ++i) {
-          q[i] = s4[i];
-          xo[i] = s4[i];
-        }
-      }
-    } else if constexpr (KIND == PSYN_REACHER) {
-      // ReacherPlanar-v0 (k_reach_step arithmetic): lane 0 of each env's lane group steps the env
-      // from both of its actions, ACT[r * 24 + 0] and [+ 1] (written by other lanes before the
-      // barrier above). The goal slots q[4], q[5] are written by a reset only.
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          reach_reset_dev(rc, rs, s6);
-          reach_obs(s6, o10);
-          q[4] = s6[4];  // a new goal with the new episode
-          q[5] = s6[5];
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EVI[EV_AR * R + r] = 0;
-        } else {
-#pragma unroll
-          for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
-          const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi),
-                                           fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi)};
-          const float rw = reach_step(s6, ac, o10);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= REACH_MAX_STEPS;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-            const unsigned slot = atomicAdd(a.count, 1u);
-            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = s6[i];
-#pragma unroll
-        for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = o10[i];
-      }
-    } else if constexpr (KIND == PSYN_QUADROTOR) {
-      // QuadrotorHover-v0 (k_quad_step arithmetic): lane 0 of each env's lane group steps the env
-      // from its four actions, ACT[r * 24 + 0..3], in place on the env's LDS rows (state in Q,
-      // observation into XO); an episode that terminates or is truncated is one event
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          quad_reset_dev(rc, rs, q);
-          quad_obs(q, xo);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EVI[EV_AR * R + r] = 0;
-        } else {
-          const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi),
-                                          fminf(fmaxf(ACT[r * 24 + 2], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 3], a.lo), a.hi)};
-          float te;
-          const float rw = quad_step(q, ac, xo, &te);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool fin = (te != 0.0f) || tt >= QUAD_MAX_STEPS;  // done = terminated or truncated
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (fin) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-            const unsigned slot = atomicAdd(a.count, 1u);
-            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
-          }
-          EVI[EV_AR * R + r] = fin ? 1 : 0;
+        const EnvLaneOut o = env_lane_step<KIND, R>(EV, r, Q + r * LDQ, XO + r * LDQ, ACT + r * 24, a.lo, a.hi);
+        if (o.fin) {
+          const unsigned slot = atomicAdd(a.count, 1u);
+          if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, o.epl, o.epr};
         }
       }
     } else {
@@ -426,12 +261,12 @@ static int launch_eval_t(const EvalArgs& a, hipStream_t s) {
 int launch_eval(const EvalArgs& a, hipStream_t s) {
   if (eval_supported(a.K) != 0 || a.env.w.on || a.nE <= 0 || a.T <= 0) return -1;
   if (a.mode != PPO_SAMPLE && a.mode != PPO_MEAN && a.mode != PPO_ROACH) return -1;
-  if (a.env.kind == PSYN_PENDULUM) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_PENDULUM>(a, s) : -1;
-  if (a.env.kind == PSYN_CARTPOLE) return (a.K.OP == 16 && a.K.A == 1) ? launch_eval_t<1, PSYN_CARTPOLE>(a, s) : -1;
-  if (a.env.kind == PSYN_REACHER)
-    return (a.K.OP == 16 && a.K.A == REACH_ACT_DIM) ? launch_eval_t<1, PSYN_REACHER>(a, s) : -1;
-  if (a.env.kind == PSYN_QUADROTOR)
-    return (a.K.OP == 32 && a.K.A == QUAD_ACT_DIM) ? launch_eval_t<2, PSYN_QUADROTOR>(a, s) : -1;
-  if (a.env.kind != PSYN_CHEETAH) return -1;
+  if (a.env.kind != PSYN_CHEETAH)  // a kind with a DevEnv, at its own tile shape and action width; no kind: -1
+    return dispatch_env_kind(a.env.kind, [&](auto KIND_) {
+      constexpr int KIND = decltype(KIND_)::value;
+      using D = DevEnv<KIND>;
+      static_assert(D::NHT == 1, "k_eval: one head tile");
+      return (a.K.OP == 16 * D::NTO && a.K.A == D::A) ? launch_eval_t<D::NTO, KIND>(a, s) : -1;
+    });
   return a.K.OP == 16 ? launch_eval_t<1>(a, s) : launch_eval_t<2>(a, s);
 }

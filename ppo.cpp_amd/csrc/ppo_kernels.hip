@@ -13,17 +13,13 @@
 //   k_gae        GAE(lambda) (ppo:447-467) — op-for-op fp32, bit-exact with the reference formula
 //   k_perm / k_adv_*  minibatch permutation and (distributed) advantage statistics (ac:830-849)
 //   k_synth_*    synthetic HalfCheetah-shaped device env (bench/test env; not the hot path)
-//   k_pend_*     Pendulum-v1 device env, per-step form (the fused form is in ppo_rollout.hip / ppo_eval.hip)
-//   k_cart_*     CartPoleContinuous-v1 device env (it terminates), per-step form (fused form: as k_pend_*)
-//   k_reach_*    ReacherPlanar-v0 device env (O = 10, A = 2, a goal per episode), per-step form (fused form: as k_pend_*)
-//   k_quad_*     QuadrotorHover-v0 device env (O = 18, A = 4, it terminates), per-step form (fused form: as k_pend_*)
+//   k_env_*      the device envs with dynamics of their own (DevEnv<KIND>, ppo_env_kinds.hpp: Pendulum-v1,
+//                CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0), per-step form (the fused
+//                form is env_lane_step in ppo_rollout.hip / ppo_eval.hip)
 #include "ppo_agent.hpp"
 #include "ppo_kernels.hpp"
 #include "ppo_wrap.hpp"
-#include "ppo_pendulum_dev.hpp"
-#include "ppo_cartpole_dev.hpp"
-#include "ppo_reacher_dev.hpp"
-#include "ppo_quadrotor_dev.hpp"
+#include "ppo_env_kinds.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2438,27 +2434,32 @@ __global__ __launch_bounds__(256) void k_synth_step_wide(SynthArgs a, int e0, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// PSYN_PENDULUM (Pendulum-v1, O = 3, A = 1): one lane per env. The vector-env bookkeeping
-// (next-step autoreset with reward 0 / done 0, episode statistics, wrapper chain) is k_synth_step's;
-// the dynamics are include/ppo_pendulum.h, bit for bit the host env gymcpp/pendulum.h.
+// The env kinds with a DevEnv (ppo_env_kinds.hpp): one lane per env. The vector-env bookkeeping
+// (next-step autoreset with reward 0 / done 0, episode statistics, wrapper chain) is k_synth_step's,
+// with one difference: an episode may terminate. The step's termination flag te goes to
+// NormalizeReward (wrap_reward; always 0 for a kind that never terminates), done = te or truncated,
+// and an episode is finished (statistics, autoreset) on either. The dynamics are DevEnv<KIND>'s, bit
+// for bit the kind's host env. The env's row of q holds DevEnv<KIND>::S state floats; Reacher's goal
+// (q[4], q[5]) is set by a reset only: the step stores back the goal it loaded.
 // ---------------------------------------------------------------------------------------------
-PPO_DEV void pend_store_obs(const SynthArgs& a, int e, float oc, const float* o3, float* obs) {
-  for (int i = 0; i < PEND_OBS_DIM; ++i)
-    obs[(long)e * PEND_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, PEND_OBS_DIM, i, oc, o3[i]) : o3[i];
+template <int O>
+PPO_DEV void env_store_obs(const SynthArgs& a, int e, float oc, const float* o, float* obs) {
+  for (int i = 0; i < O; ++i) obs[(long)e * O + i] = a.w.on ? wrap_obs_dim(a.w, e, O, i, oc, o[i]) : o[i];
   if (a.w.on) a.w.ocount[e] = oc + 1.0f;
 }
 
-__global__ __launch_bounds__(256) void k_pend_reset(SynthArgs a, int seed, float* obs, float* done) {
+template <int KIND>
+__global__ __launch_bounds__(256) void k_env_reset(SynthArgs a, int seed, float* obs, float* done) {
+  using D = DevEnv<KIND>;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.E) return;
   if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
   const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-  float th, thd, o3[PEND_OBS_DIM];
-  pend_reset_dev(rc, rs, &th, &thd);
-  pend_obs(th, thd, o3);
-  float* q = a.q + (long)e * PEND_OBS_DIM;
-  q[0] = th; q[1] = thd; q[2] = 0.0f;
-  pend_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o3, obs);
+  float s[D::S], o[D::O];
+  D::reset(rc, rs, s, o);
+  float* q = a.q + (long)e * D::O;
+  for (int i = 0; i < D::S; ++i) q[i] = s[i];  // the slots S..O-1 are zero from creation on
+  env_store_obs<D::O>(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o, obs);
   a.rcount[e] = rc + 1;
   a.t[e] = 0;
   a.ep_ret[e] = 0.0f;
@@ -2467,21 +2468,22 @@ __global__ __launch_bounds__(256) void k_pend_reset(SynthArgs a, int seed, float
   if (done) done[e] = 0.0f;
 }
 
-__global__ __launch_bounds__(256) void k_pend_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
-                                                   float lo, float hi, float* __restrict__ obs,
-                                                   float* __restrict__ reward, float* __restrict__ done) {
+template <int KIND>
+__global__ __launch_bounds__(256) void k_env_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
+                                                  float lo, float hi, float* __restrict__ obs,
+                                                  float* __restrict__ reward, float* __restrict__ done) {
 #pragma clang fp contract(off)
+  using D = DevEnv<KIND>;
   const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= e1) return;
-  float* __restrict__ q = a.q + (long)e * PEND_OBS_DIM;
+  float* __restrict__ q = a.q + (long)e * D::O;
   const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
-  float th, thd, o3[PEND_OBS_DIM];
+  float s[D::S], o[D::O];
   if (a.autoreset[e] != 0) {
     const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-    pend_reset_dev(rc, rs, &th, &thd);
-    pend_obs(th, thd, o3);
-    q[0] = th; q[1] = thd;
-    pend_store_obs(a, e, oc, o3, obs);
+    D::reset(rc, rs, s, o);
+    for (int i = 0; i < D::S; ++i) q[i] = s[i];
+    env_store_obs<D::O>(a, e, oc, o, obs);
     a.rcount[e] = rc + 1;
     a.t[e] = 0;
     a.ep_ret[e] = 0.0f;
@@ -2491,245 +2493,17 @@ __global__ __launch_bounds__(256) void k_pend_step(SynthArgs a, int e0, int e1, 
     a.autoreset[e] = 0;
     return;
   }
-  th = q[0]; thd = q[1];
-  const float ac = fminf(fmaxf(act[e - e0], lo), hi);  // clip_actions; the dynamics clip to +-2 themselves
-  const float r = pend_step(&th, &thd, ac, o3);
-  q[0] = th; q[1] = thd;
-  pend_store_obs(a, e, oc, o3, obs);
-  const int t = a.t[e] + 1;
-  a.t[e] = t;
-  const bool tr = t >= PEND_MAX_STEPS;
-  reward[e] = a.w.on ? wrap_reward(a.w, e, r, 0.0f) : r;  // Pendulum never terminates
-  done[e] = tr ? 1.0f : 0.0f;
-  a.ep_ret[e] = (a.ep_ret[e] + r);
-  a.ep_len[e] += 1;
-  if (tr) {
-    a.fin_ret[e] += a.ep_ret[e];
-    a.fin_len[e] += (float)a.ep_len[e];
-    a.fin_cnt[e] += 1.0f;
-  }
-  a.autoreset[e] = tr ? 1 : 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// PSYN_CARTPOLE (CartPoleContinuous-v1, O = 4, A = 1): one lane per env, the bookkeeping of
-// k_pend_step with one difference: the episodes terminate. The step's termination flag te goes to
-// NormalizeReward (wrap_reward), done = te or truncated, and an episode is finished (statistics,
-// autoreset) on either. The dynamics are include/ppo_cartpole.h, bit for bit gymcpp/cartpole.h.
-// ---------------------------------------------------------------------------------------------
-PPO_DEV void cart_store_obs(const SynthArgs& a, int e, float oc, const float* s4, float* obs) {
-  for (int i = 0; i < CART_OBS_DIM; ++i)
-    obs[(long)e * CART_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, CART_OBS_DIM, i, oc, s4[i]) : s4[i];
-  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
-}
-
-__global__ __launch_bounds__(256) void k_cart_reset(SynthArgs a, int seed, float* obs, float* done) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= a.E) return;
-  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
-  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-  float s4[CART_OBS_DIM];
-  cart_reset_dev(rc, rs, s4);
-  float* q = a.q + (long)e * CART_OBS_DIM;
-  for (int i = 0; i < CART_OBS_DIM; ++i) q[i] = s4[i];
-  cart_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, s4, obs);
-  a.rcount[e] = rc + 1;
-  a.t[e] = 0;
-  a.ep_ret[e] = 0.0f;
-  a.ep_len[e] = 0;
-  a.autoreset[e] = 0;
-  if (done) done[e] = 0.0f;
-}
-
-__global__ __launch_bounds__(256) void k_cart_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
-                                                   float lo, float hi, float* __restrict__ obs,
-                                                   float* __restrict__ reward, float* __restrict__ done) {
-#pragma clang fp contract(off)
-  const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= e1) return;
-  float* __restrict__ q = a.q + (long)e * CART_OBS_DIM;
-  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
-  float s4[CART_OBS_DIM];
-  if (a.autoreset[e] != 0) {
-    const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-    cart_reset_dev(rc, rs, s4);
-    for (int i = 0; i < CART_OBS_DIM; ++i) q[i] = s4[i];
-    cart_store_obs(a, e, oc, s4, obs);
-    a.rcount[e] = rc + 1;
-    a.t[e] = 0;
-    a.ep_ret[e] = 0.0f;
-    a.ep_len[e] = 0;
-    reward[e] = 0.0f;
-    done[e] = 0.0f;
-    a.autoreset[e] = 0;
-    return;
-  }
-  for (int i = 0; i < CART_OBS_DIM; ++i) s4[i] = q[i];
-  const float ac = fminf(fmaxf(act[e - e0], lo), hi);  // clip_actions; the dynamics clip to +-1 themselves
+  for (int i = 0; i < D::S; ++i) s[i] = q[i];
+  const float* __restrict__ ar = act + (long)(e - e0) * D::A;
+  float ac[D::A];  // clip_actions, per dimension; the dynamics clip to their own range themselves
+  for (int k = 0; k < D::A; ++k) ac[k] = fminf(fmaxf(ar[k], lo), hi);
   float te;
-  const float r = cart_step(s4, ac, &te);
-  for (int i = 0; i < CART_OBS_DIM; ++i) q[i] = s4[i];
-  cart_store_obs(a, e, oc, s4, obs);
+  const float r = D::step(s, ac, o, &te);
+  for (int i = 0; i < D::S; ++i) q[i] = s[i];
+  env_store_obs<D::O>(a, e, oc, o, obs);
   const int t = a.t[e] + 1;
   a.t[e] = t;
-  const bool fin = (te != 0.0f) || t >= CART_MAX_STEPS;  // done = terminated or truncated
-  reward[e] = a.w.on ? wrap_reward(a.w, e, r, te) : r;
-  done[e] = fin ? 1.0f : 0.0f;
-  a.ep_ret[e] = (a.ep_ret[e] + r);
-  a.ep_len[e] += 1;
-  if (fin) {
-    a.fin_ret[e] += a.ep_ret[e];
-    a.fin_len[e] += (float)a.ep_len[e];
-    a.fin_cnt[e] += 1.0f;
-  }
-  a.autoreset[e] = fin ? 1 : 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// PSYN_REACHER (ReacherPlanar-v0, O = 10, A = 2): one lane per env, the bookkeeping of k_cart_step.
-// The episodes never terminate (the flag passed to wrap_reward is 0; done = truncated after 50
-// steps). The state q[0..5] = (q1, q2, q1dot, q2dot, gx, gy); the goal slots are written by a reset
-// only. The step reads both actions of the env. The dynamics are include/ppo_reacher.h, bit for
-// bit gymcpp/reacher.h.
-// ---------------------------------------------------------------------------------------------
-PPO_DEV void reach_store_obs(const SynthArgs& a, int e, float oc, const float* o10, float* obs) {
-  for (int i = 0; i < REACH_OBS_DIM; ++i)
-    obs[(long)e * REACH_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, REACH_OBS_DIM, i, oc, o10[i]) : o10[i];
-  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
-}
-
-__global__ __launch_bounds__(256) void k_reach_reset(SynthArgs a, int seed, float* obs, float* done) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= a.E) return;
-  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
-  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-  float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
-  reach_reset_dev(rc, rs, s6);
-  reach_obs(s6, o10);
-  float* q = a.q + (long)e * REACH_OBS_DIM;
-  for (int i = 0; i < REACH_STATE_DIM; ++i) q[i] = s6[i];
-  reach_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o10, obs);
-  a.rcount[e] = rc + 1;
-  a.t[e] = 0;
-  a.ep_ret[e] = 0.0f;
-  a.ep_len[e] = 0;
-  a.autoreset[e] = 0;
-  if (done) done[e] = 0.0f;
-}
-
-__global__ __launch_bounds__(256) void k_reach_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
-                                                    float lo, float hi, float* __restrict__ obs,
-                                                    float* __restrict__ reward, float* __restrict__ done) {
-#pragma clang fp contract(off)
-  const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= e1) return;
-  float* __restrict__ q = a.q + (long)e * REACH_OBS_DIM;
-  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
-  float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
-  if (a.autoreset[e] != 0) {
-    const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-    reach_reset_dev(rc, rs, s6);
-    reach_obs(s6, o10);
-    for (int i = 0; i < REACH_STATE_DIM; ++i) q[i] = s6[i];  // a new goal with the new episode
-    reach_store_obs(a, e, oc, o10, obs);
-    a.rcount[e] = rc + 1;
-    a.t[e] = 0;
-    a.ep_ret[e] = 0.0f;
-    a.ep_len[e] = 0;
-    reward[e] = 0.0f;
-    done[e] = 0.0f;
-    a.autoreset[e] = 0;
-    return;
-  }
-  for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
-  const float* __restrict__ ar = act + (long)(e - e0) * REACH_ACT_DIM;
-  // clip_actions, per dimension; the dynamics clip to +-1 themselves
-  const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ar[0], lo), hi), fminf(fmaxf(ar[1], lo), hi)};
-  const float r = reach_step(s6, ac, o10);
-  for (int i = 0; i < 4; ++i) q[i] = s6[i];  // the goal slots stay as the reset wrote them
-  reach_store_obs(a, e, oc, o10, obs);
-  const int t = a.t[e] + 1;
-  a.t[e] = t;
-  const bool tr = t >= REACH_MAX_STEPS;
-  reward[e] = a.w.on ? wrap_reward(a.w, e, r, 0.0f) : r;  // the arm never terminates
-  done[e] = tr ? 1.0f : 0.0f;
-  a.ep_ret[e] = (a.ep_ret[e] + r);
-  a.ep_len[e] += 1;
-  if (tr) {
-    a.fin_ret[e] += a.ep_ret[e];
-    a.fin_len[e] += (float)a.ep_len[e];
-    a.fin_cnt[e] += 1.0f;
-  }
-  a.autoreset[e] = tr ? 1 : 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// PSYN_QUADROTOR (QuadrotorHover-v0, O = 18, A = 4): one lane per env, the bookkeeping of
-// k_cart_step: the episodes terminate (|p|^2 > 9) and truncate (500 steps), the termination flag
-// goes to wrap_reward. The state q[0..12] = (p, v, quaternion, omega). The step reads all four
-// actions of the env. The dynamics are include/ppo_quadrotor.h, bit for bit gymcpp/quadrotor.h.
-// ---------------------------------------------------------------------------------------------
-PPO_DEV void quad_store_obs(const SynthArgs& a, int e, float oc, const float* o18, float* obs) {
-  for (int i = 0; i < QUAD_OBS_DIM; ++i)
-    obs[(long)e * QUAD_OBS_DIM + i] = a.w.on ? wrap_obs_dim(a.w, e, QUAD_OBS_DIM, i, oc, o18[i]) : o18[i];
-  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
-}
-
-__global__ __launch_bounds__(256) void k_quad_reset(SynthArgs a, int seed, float* obs, float* done) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= a.E) return;
-  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
-  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-  float s13[QUAD_STATE_DIM], o18[QUAD_OBS_DIM];
-  quad_reset_dev(rc, rs, s13);
-  quad_obs(s13, o18);
-  float* q = a.q + (long)e * QUAD_OBS_DIM;
-  for (int i = 0; i < QUAD_STATE_DIM; ++i) q[i] = s13[i];
-  quad_store_obs(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o18, obs);
-  a.rcount[e] = rc + 1;
-  a.t[e] = 0;
-  a.ep_ret[e] = 0.0f;
-  a.ep_len[e] = 0;
-  a.autoreset[e] = 0;
-  if (done) done[e] = 0.0f;
-}
-
-__global__ __launch_bounds__(256) void k_quad_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
-                                                   float lo, float hi, float* __restrict__ obs,
-                                                   float* __restrict__ reward, float* __restrict__ done) {
-#pragma clang fp contract(off)
-  const int e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= e1) return;
-  float* __restrict__ q = a.q + (long)e * QUAD_OBS_DIM;
-  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
-  float s13[QUAD_STATE_DIM], o18[QUAD_OBS_DIM];
-  if (a.autoreset[e] != 0) {
-    const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-    quad_reset_dev(rc, rs, s13);
-    quad_obs(s13, o18);
-    for (int i = 0; i < QUAD_STATE_DIM; ++i) q[i] = s13[i];
-    quad_store_obs(a, e, oc, o18, obs);
-    a.rcount[e] = rc + 1;
-    a.t[e] = 0;
-    a.ep_ret[e] = 0.0f;
-    a.ep_len[e] = 0;
-    reward[e] = 0.0f;
-    done[e] = 0.0f;
-    a.autoreset[e] = 0;
-    return;
-  }
-  for (int i = 0; i < QUAD_STATE_DIM; ++i) s13[i] = q[i];
-  const float* __restrict__ ar = act + (long)(e - e0) * QUAD_ACT_DIM;
-  // clip_actions, per dimension; the dynamics clip to +-1 themselves
-  const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ar[0], lo), hi), fminf(fmaxf(ar[1], lo), hi),
-                                  fminf(fmaxf(ar[2], lo), hi), fminf(fmaxf(ar[3], lo), hi)};
-  float te;
-  const float r = quad_step(s13, ac, o18, &te);
-  for (int i = 0; i < QUAD_STATE_DIM; ++i) q[i] = s13[i];
-  quad_store_obs(a, e, oc, o18, obs);
-  const int t = a.t[e] + 1;
-  a.t[e] = t;
-  const bool fin = (te != 0.0f) || t >= QUAD_MAX_STEPS;  // done = terminated or truncated
+  const bool fin = (te != 0.0f) || t >= D::MAX_STEPS;  // done = terminated or truncated
   reward[e] = a.w.on ? wrap_reward(a.w, e, r, te) : r;
   done[e] = fin ? 1.0f : 0.0f;
   a.ep_ret[e] = (a.ep_ret[e] + r);
@@ -2981,46 +2755,21 @@ void launch_wrap_step(const WrapArgs& w, int O, int e0, int e1, float* obs, floa
   hipLaunchKernelGGL(k_wrap_step, dim3((e1 - e0 + 3) / 4), dim3(256), 0, s, w, O, e0, e1, obs, reward, term, is_reset);
 }
 void launch_synth_reset(const SynthArgs& a, int seed, float* obs, float* done, hipStream_t s) {
-  if (a.kind == PSYN_PENDULUM) {
-    hipLaunchKernelGGL(k_pend_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
-    return;
-  }
-  if (a.kind == PSYN_CARTPOLE) {
-    hipLaunchKernelGGL(k_cart_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
-    return;
-  }
-  if (a.kind == PSYN_REACHER) {
-    hipLaunchKernelGGL(k_reach_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
-    return;
-  }
-  if (a.kind == PSYN_QUADROTOR) {
-    hipLaunchKernelGGL(k_quad_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
-    return;
-  }
+  const int rc = dispatch_env_kind(a.kind, [&](auto KIND_) {
+    hipLaunchKernelGGL(k_env_reset<decltype(KIND_)::value>, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
+    return 0;
+  });
+  if (rc == 0) return;  // a kind with a DevEnv; every other env is the synthetic cheetah
   hipLaunchKernelGGL(k_synth_reset, dim3((a.E + 255) / 256), dim3(256), 0, s, a, seed, obs, done);
 }
 void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, float lo, float hi, float* obs,
                        float* reward, float* done, hipStream_t s) {
-  if (a.kind == PSYN_PENDULUM) {
-    hipLaunchKernelGGL(k_pend_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
-                       done);
-    return;
-  }
-  if (a.kind == PSYN_CARTPOLE) {
-    hipLaunchKernelGGL(k_cart_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
-                       done);
-    return;
-  }
-  if (a.kind == PSYN_REACHER) {
-    hipLaunchKernelGGL(k_reach_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
-                       done);
-    return;
-  }
-  if (a.kind == PSYN_QUADROTOR) {
-    hipLaunchKernelGGL(k_quad_step, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
-                       done);
-    return;
-  }
+  const int rc = dispatch_env_kind(a.kind, [&](auto KIND_) {
+    hipLaunchKernelGGL(k_env_step<decltype(KIND_)::value>, dim3((e1 - e0 + 255) / 256), dim3(256), 0, s, a, e0, e1, act,
+                       lo, hi, obs, reward, done);
+    return 0;
+  });
+  if (rc == 0) return;  // a kind with a DevEnv; every other env is the synthetic cheetah
   if (a.O > 32) {
     hipLaunchKernelGGL(k_synth_step_wide, dim3((e1 - e0 + 3) / 4), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs,
                        reward, done);
@@ -3029,3 +2778,4 @@ void launch_synth_step(const SynthArgs& a, int e0, int e1, const float* act, flo
   hipLaunchKernelGGL(k_synth_step, dim3((e1 - e0 + 7) / 8), dim3(256), 0, s, a, e0, e1, act, lo, hi, obs, reward,
                      done);
 }
+

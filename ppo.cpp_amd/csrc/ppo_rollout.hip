@@ -19,10 +19,6 @@
 // (tests/test_gpu_rollout.py).
 #include "ppo_act_common.hpp"
 #include "ppo_wrap.hpp"
-#include "ppo_pendulum_dev.hpp"
-#include "ppo_cartpole_dev.hpp"
-#include "ppo_reacher_dev.hpp"
-#include "ppo_quadrotor_dev.hpp"
 
 #include <type_traits>
 
@@ -56,19 +52,19 @@ constexpr int kRdbgEnv = 26;
 #define ROLL_STAMP(t, k) do {} while (0)
 #endif
 
-// RollGeo, the EV_* slots, stage_params, trunk_rows, load_weight_slices (shared with ppo_eval.hip)
+// RollGeo, the EV_* slots, env_lane_step, stage_params, trunk_rows, load_weight_slices (shared with ppo_eval.hip)
 #include "ppo_rollout_common.hpp"
 
 // =============================================================================================
 // k_rollout: T steps of {actor act + sample, synthetic env step} for 16 envs per workgroup
 // =============================================================================================
-// KIND: the device env's kind (PSYN_CHEETAH | PSYN_PENDULUM | PSYN_CARTPOLE | PSYN_REACHER |
-// PSYN_QUADROTOR), a compile-time parameter so that the cheetah instantiations carry nothing of the
-// Pendulum, CartPole, Reacher or Quadrotor step (and compile to the code they had). The kind is
-// independent of the tile count: psyn_kind_tiles_ok names the shapes each kind is built at.
+// KIND: the device env's kind (PSYN_CHEETAH, or a kind with a DevEnv: ppo_env_kinds.hpp), a
+// compile-time parameter so that the cheetah instantiations carry nothing of another kind's step (and
+// compile to the code they had). The kind is independent of the tile count: DevEnv<KIND>::NTO / NHT
+// name the shape each kind is built at (psyn_kind_tiles_ok).
 template <int NTO, int NHT, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
-  static_assert(psyn_kind_tiles_ok(KIND, NTO, NHT), PSYN_KIND_TILES_MSG);
+  static_assert(psyn_kind_tiles_ok<KIND, NTO, NHT>(), PSYN_KIND_TILES_MSG);
   using GE = RollGeo<NTO, NHT>;
   constexpr int OP = GE::OP, LDX = GE::LDX, LDP = GE::LDP, LDQ = GE::LDQ, R = kRows;
   constexpr int NCH = (OP + 31) / 32;  // 32-dim chunks of the env state per env lane group
@@ -220,188 +216,16 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
     }
     ROLL_STAMP(t, 3);
     // ---- env step: 32 lanes per env ----
-    if constexpr (KIND == PSYN_PENDULUM) {
-      // Pendulum-v1 (k_pend_step arithmetic): lane 0 of each env's lane group steps the env
+    if constexpr (KIND != PSYN_CHEETAH) {
+      // a kind with a DevEnv (k_env_step arithmetic): lane 0 of each env's lane group steps the env
+      // from its actions ACT[r * 24 + 0..A-1] (written by other lanes before the barrier above). No
+      // wrapper chain in this kernel: the termination flag feeds done only.
 #pragma clang fp contract(off)
       const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
       if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float th, thd, o3[PEND_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          pend_reset_dev(rc, rs, &th, &thd);
-          pend_obs(th, thd, o3);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-          th = q[0];
-          thd = q[1];
-          const float rw = pend_step(&th, &thd, fminf(fmaxf(ACT[r * 24], a.lo), a.hi), o3);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= PEND_MAX_STEPS;
-          a.s_rewards[(long)t * E + e] = rw;
-          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
-        q[0] = th;
-        q[1] = thd;
-#pragma unroll
-        for (int i = 0; i < PEND_OBS_DIM; ++i) xo[i] = o3[i];
-      }
-    } else if constexpr (KIND == PSYN_CARTPOLE) {
-      // CartPoleContinuous-v1 (k_cart_step arithmetic): lane 0 of each env's lane group steps the
-      // env; an episode ends on termination or truncation, on any step, env by env
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float s4[CART_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          cart_reset_dev(rc, rs, s4);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-#pragma unroll
-          for (int i = 0; i < CART_OBS_DIM; ++i) s4[i] = q[i];
-          float te;
-          const float rw = cart_step(s4, fminf(fmaxf(ACT[r * 24], a.lo), a.hi), &te);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool fin = (te != 0.0f) || tt >= CART_MAX_STEPS;  // done = terminated or truncated
-          a.s_rewards[(long)t * E + e] = rw;  // (no wrapper chain in this kernel: te feeds done only)
-          EV[EV_DONE * R + r] = fin ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (fin) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = fin ? 1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < CART_OBS_DIM; ++i) {
-          q[i] = s4[i];
-          xo[i] = s4[i];
-        }
-      }
-    } else if constexpr (KIND == PSYN_REACHER) {
-      // ReacherPlanar-v0 (k_reach_step arithmetic): lane 0 of each env's lane group steps the env
-      // from both of its actions, ACT[r * 24 + 0] and [+ 1] (written by other lanes before the
-      // barrier above). The goal slots q[4], q[5] are written by a reset only.
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          reach_reset_dev(rc, rs, s6);
-          reach_obs(s6, o10);
-          q[4] = s6[4];  // a new goal with the new episode
-          q[5] = s6[5];
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-#pragma unroll
-          for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
-          const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi),
-                                           fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi)};
-          const float rw = reach_step(s6, ac, o10);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= REACH_MAX_STEPS;
-          a.s_rewards[(long)t * E + e] = rw;
-          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = s6[i];
-#pragma unroll
-        for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = o10[i];
-      }
-    } else if constexpr (KIND == PSYN_QUADROTOR) {
-      // QuadrotorHover-v0 (k_quad_step arithmetic): lane 0 of each env's lane group steps the env
-      // from its four actions, ACT[r * 24 + 0..3] (written by other lanes before the barrier above).
-      // The step works on the env's LDS rows in place (state in Q, observation into XO) instead of
-      // carrying 13 + 18 values in registers next to the resident weights.
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          quad_reset_dev(rc, rs, q);
-          quad_obs(q, xo);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-          const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ACT[r * 24 + 0], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 1], a.lo), a.hi),
-                                          fminf(fmaxf(ACT[r * 24 + 2], a.lo), a.hi), fminf(fmaxf(ACT[r * 24 + 3], a.lo), a.hi)};
-          float te;
-          const float rw = quad_step(q, ac, xo, &te);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool fin = (te != 0.0f) || tt >= QUAD_MAX_STEPS;  // done = terminated or truncated
-          a.s_rewards[(long)t * E + e] = rw;  // (no wrapper chain in this kernel: te feeds done only)
-          EV[EV_DONE * R + r] = fin ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (fin) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = fin ? 1 : 0;
-        }
+        const EnvLaneOut o = env_lane_step<KIND, R>(EV, r, Q + r * LDQ, XO + r * LDQ, ACT + r * 24, a.lo, a.hi);
+        a.s_rewards[(long)t * E + e] = o.reward;
+        EV[EV_DONE * R + r] = o.fin ? 1.0f : 0.0f;
       }
     } else {
       // the synthetic cheetah (k_synth_step / k_synth_step_wide arithmetic)
@@ -683,7 +507,7 @@ PPO_DEV f4 trunk4(const f4 (&xv)[NKW], const f4 (&wa)[NKW][4], const f4 (&w2v)[4
 // the VALU-bound wrapper chain a quarter.
 template <int NTO, int NHT, int RR, int KIND = PSYN_CHEETAH>
 __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
-  static_assert(psyn_kind_tiles_ok(KIND, NTO, NHT), PSYN_KIND_TILES_MSG);
+  static_assert(psyn_kind_tiles_ok<KIND, NTO, NHT>(), PSYN_KIND_TILES_MSG);
   constexpr int H = kR4H, R = RR, OP = NTO * 16, NKW = (NTO + 3) / 4, NHP = NHT * 16;
   constexpr int LPE = kR4Threads / RR;  // env lanes per env (one env within one wave)
   constexpr int LDQ = Roll4Geo<NTO, NHT>::LDQ, NCE = (OP + LPE - 1) / LPE, kEnvGroup = 12;
@@ -850,220 +674,26 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
     ROLL_STAMP(t, 3);
     // ---- env step (wrapper chain fused): LPE lanes per env, all RR envs at once (the per-env
     // reward / episode bookkeeping of lane 0 runs once per step) ----
-    if constexpr (KIND == PSYN_PENDULUM) {
-      // Pendulum-v1 (k_pend_step arithmetic): lane 0 of each env's lane group steps the env
+    if constexpr (KIND != PSYN_CHEETAH) {
+      // a kind with a DevEnv (k_env_step arithmetic): lane 0 of each env's lane group steps the env
+      // from its actions ACT[r * 32 + 0..A-1] (written by other lanes before the barrier above). The
+      // step's termination flag goes to NormalizeReward (a reset step's reward 0 does not pass through
+      // it); the raw observation lies in XO, which the wrapper chain normalises where it lies.
 #pragma clang fp contract(off)
       const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
       if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
         float* xo = XO + r * LDQ;
-        float* om = WOM + r * LDQ;
-        float* ov = WOV + r * LDQ;
-        const float oc = EV[EV_WOC * R + r];
-        float th, thd, o3[PEND_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          pend_reset_dev(rc, rs, &th, &thd);
-          pend_obs(th, thd, o3);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-          th = q[0];
-          thd = q[1];
-          const float rw = pend_step(&th, &thd, fminf(fmaxf(ACT[r * 32], a.lo), a.hi), o3);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= PEND_MAX_STEPS;
-          a.s_rewards[(long)t * E + e] =
-              w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
-                                    EV + EV_WRC * R + r, w.gamma, rw, 0.0f)
-                   : rw;
-          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
-        q[0] = th;
-        q[1] = thd;
-#pragma unroll
-        for (int i = 0; i < PEND_OBS_DIM; ++i) xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, o3[i]) : o3[i];
-        if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
-      }
-    } else if constexpr (KIND == PSYN_CARTPOLE) {
-      // CartPoleContinuous-v1 (k_cart_step arithmetic): lane 0 of each env's lane group steps the
-      // env. The step's termination flag te goes to NormalizeReward; an episode ends on termination
-      // or truncation, on any step, env by env.
-#pragma clang fp contract(off)
-      const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float* om = WOM + r * LDQ;
-        float* ov = WOV + r * LDQ;
-        const float oc = EV[EV_WOC * R + r];
-        float s4[CART_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          cart_reset_dev(rc, rs, s4);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-#pragma unroll
-          for (int i = 0; i < CART_OBS_DIM; ++i) s4[i] = q[i];
-          float te;
-          const float rw = cart_step(s4, fminf(fmaxf(ACT[r * 32], a.lo), a.hi), &te);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool fin = (te != 0.0f) || tt >= CART_MAX_STEPS;  // done = terminated or truncated
-          a.s_rewards[(long)t * E + e] =
-              w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
-                                    EV + EV_WRC * R + r, w.gamma, rw, te)
-                   : rw;
-          EV[EV_DONE * R + r] = fin ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (fin) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = fin ? 1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < CART_OBS_DIM; ++i) {
-          q[i] = s4[i];
-          xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, s4[i]) : s4[i];
-        }
-        if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
-      }
-    } else if constexpr (KIND == PSYN_REACHER) {
-      // ReacherPlanar-v0 (k_reach_step arithmetic): lane 0 of each env's lane group steps the env
-      // from both of its actions, ACT[r * 32 + 0] and [+ 1] (written by other lanes before the
-      // barrier above). The goal slots q[4], q[5] are written by a reset only. The termination
-      // flag passed to NormalizeReward is always 0.
-#pragma clang fp contract(off)
-      const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float* om = WOM + r * LDQ;
-        float* ov = WOV + r * LDQ;
-        const float oc = EV[EV_WOC * R + r];
-        float s6[REACH_STATE_DIM], o10[REACH_OBS_DIM];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          reach_reset_dev(rc, rs, s6);
-          reach_obs(s6, o10);
-          q[4] = s6[4];  // a new goal with the new episode
-          q[5] = s6[5];
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-#pragma unroll
-          for (int i = 0; i < REACH_STATE_DIM; ++i) s6[i] = q[i];
-          const float ac[REACH_ACT_DIM] = {fminf(fmaxf(ACT[r * 32 + 0], a.lo), a.hi),
-                                           fminf(fmaxf(ACT[r * 32 + 1], a.lo), a.hi)};
-          const float rw = reach_step(s6, ac, o10);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= REACH_MAX_STEPS;
-          a.s_rewards[(long)t * E + e] =
-              w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
-                                    EV + EV_WRC * R + r, w.gamma, rw, 0.0f)
-                   : rw;
-          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = s6[i];
-#pragma unroll
-        for (int i = 0; i < REACH_OBS_DIM; ++i) xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, o10[i]) : o10[i];
-        if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
-      }
-    } else if constexpr (KIND == PSYN_QUADROTOR) {
-      // QuadrotorHover-v0 (k_quad_step arithmetic): lane 0 of each env's lane group steps the env
-      // from its four actions, ACT[r * 32 + 0..3] (written by other lanes before the barrier above).
-      // The step's termination flag te goes to NormalizeReward; an episode ends on termination or
-      // truncation, on any step, env by env. The step works on the env's LDS rows in place: the state
-      // in Q, the raw observation into XO, which the wrapper chain then normalises where it lies.
-#pragma clang fp contract(off)
-      const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        float* q = Q + r * LDQ;
-        float* xo = XO + r * LDQ;
-        float* om = WOM + r * LDQ;
-        float* ov = WOV + r * LDQ;
-        const float oc = EV[EV_WOC * R + r];
-        if (EVI[EV_AR * R + r] != 0) {
-          const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-          quad_reset_dev(rc, rs, q);
-          quad_obs(q, xo);
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        } else {
-          const float ac[QUAD_ACT_DIM] = {fminf(fmaxf(ACT[r * 32 + 0], a.lo), a.hi), fminf(fmaxf(ACT[r * 32 + 1], a.lo), a.hi),
-                                          fminf(fmaxf(ACT[r * 32 + 2], a.lo), a.hi), fminf(fmaxf(ACT[r * 32 + 3], a.lo), a.hi)};
-          float te;
-          const float rw = quad_step(q, ac, xo, &te);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool fin = (te != 0.0f) || tt >= QUAD_MAX_STEPS;  // done = terminated or truncated
-          a.s_rewards[(long)t * E + e] =
-              w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
-                                    EV + EV_WRC * R + r, w.gamma, rw, te)
-                   : rw;
-          EV[EV_DONE * R + r] = fin ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (fin) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = fin ? 1 : 0;
-        }
+        const EnvLaneOut o = env_lane_step<KIND, R>(EV, r, Q + r * LDQ, xo, ACT + r * 32, a.lo, a.hi);
+        a.s_rewards[(long)t * E + e] =
+            (w.on && !o.reset) ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
+                                                EV + EV_WRC * R + r, w.gamma, o.reward, o.term)
+                               : o.reward;
+        EV[EV_DONE * R + r] = o.fin ? 1.0f : 0.0f;
         if (w.on) {
-          for (int i = 0; i < QUAD_OBS_DIM; ++i) xo[i] = wrap_obs_at(om + i, ov + i, oc, xo[i]);
+          float* om = WOM + r * LDQ;
+          float* ov = WOV + r * LDQ;
+          const float oc = EV[EV_WOC * R + r];
+          for (int i = 0; i < DevEnv<KIND>::O; ++i) xo[i] = wrap_obs_at(om + i, ov + i, oc, xo[i]);
           EV[EV_WOC * R + r] = oc + 1.0f;
         }
       }
@@ -1811,31 +1441,15 @@ int launch_rollout(const RolloutArgs& a, hipStream_t s) {
   // an explicit rollout_kernel=valu that cannot apply is an error, not a silent k_rollout
   if (a.variant == 2 && a.env.kind != PSYN_CHEETAH) return -4;
   if (a.variant == 2 && !use_rollout_v(a)) return -3;
-  if (a.env.kind == PSYN_PENDULUM) {  // O = 3, A = 1: one input tile, one head tile
-    if (a.K.OP != 16 || a.K.A != 1) return -1;
-    if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<1, 1, PSYN_PENDULUM>(a, s);
-    if (a.env.w.on) return -1;
-    return launch_rollout_t<1, 1, PSYN_PENDULUM>(a, s);
-  }
-  if (a.env.kind == PSYN_CARTPOLE) {  // O = 4, A = 1: one input tile, one head tile
-    if (a.K.OP != 16 || a.K.A != 1) return -1;
-    if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<1, 1, PSYN_CARTPOLE>(a, s);
-    if (a.env.w.on) return -1;
-    return launch_rollout_t<1, 1, PSYN_CARTPOLE>(a, s);
-  }
-  if (a.env.kind == PSYN_REACHER) {  // O = 10, A = 2: one input tile, one head tile
-    if (a.K.OP != 16 || a.K.A != REACH_ACT_DIM) return -1;
-    if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<1, 1, PSYN_REACHER>(a, s);
-    if (a.env.w.on) return -1;
-    return launch_rollout_t<1, 1, PSYN_REACHER>(a, s);
-  }
-  if (a.env.kind == PSYN_QUADROTOR) {  // O = 18, A = 4: two input tiles, one head tile
-    if (a.K.OP != 32 || a.K.A != QUAD_ACT_DIM) return -1;
-    if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<2, 1, PSYN_QUADROTOR>(a, s);
-    if (a.env.w.on) return -1;
-    return launch_rollout_t<2, 1, PSYN_QUADROTOR>(a, s);
-  }
-  if (a.env.kind != PSYN_CHEETAH) return -1;
+  if (a.env.kind != PSYN_CHEETAH)  // a kind with a DevEnv, at its own tile shape and action width; no kind: -1
+    return dispatch_env_kind(a.env.kind, [&](auto KIND_) {
+      constexpr int KIND = decltype(KIND_)::value;
+      using D = DevEnv<KIND>;
+      if (a.K.OP != 16 * D::NTO || a.K.A != D::A) return -1;
+      if (a.K.kind == PPO_NET_TANH_NORMAL) return launch_rollout4_t<D::NTO, D::NHT, KIND>(a, s);
+      if (a.env.w.on) return -1;
+      return launch_rollout_t<D::NTO, D::NHT, KIND>(a, s);
+    });
   if (use_rollout_v(a)) return a.K.OP == 16 ? launch_rollout_v_t<1>(a, s) : launch_rollout_v_t<2>(a, s);
   if (a.K.kind == PPO_NET_TANH_NORMAL) {
     const int nht = (a.K.A + 15) / 16;

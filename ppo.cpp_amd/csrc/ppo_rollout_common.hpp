@@ -1,7 +1,7 @@
 // ppo_rollout_common.hpp — building blocks of the persistent kernels of the 256-wide LayerNorm-Beta
 // agent: k_rollout / k_values (ppo_rollout.hip) and k_eval (ppo_eval.hip). LDS geometry, the per-env
-// scalar slots, the staged small parameters, the register-resident weight slices and one trunk
-// forward for the rows in XS. Kernels that use them in the same order produce bitwise identical
+// scalar slots and the env step on them (env_lane_step, also k_rollout4's), the staged small
+// parameters, the register-resident weight slices and one trunk forward for the rows in XS. Kernels that use them in the same order produce bitwise identical
 // results (and bitwise k_act3's, whose blocks of ppo_act_common.hpp they are built from).
 //
 // A translation unit of the diagnostic stamps build defines ROLL_STAMP / RDBG / kRdbgEnv before it
@@ -9,6 +9,7 @@
 #pragma once
 
 #include "ppo_act_common.hpp"
+#include "ppo_env_kinds.hpp"
 
 #include <type_traits>
 
@@ -56,6 +57,71 @@ struct RollGeo {
 // (the wrapper chain's per-env scalars: obs count, return accumulator, reward mean / var / count)
 enum { EV_DONE = 0, EV_AR, EV_T, EV_RSEED, EV_RCOUNT, EV_EPR, EV_EPL, EV_FR, EV_FL, EV_FC,
        EV_WOC, EV_WRA, EV_WRM, EV_WRV, EV_WRC, EV_NSLOT };
+
+// One env step of a kind with a DevEnv, by lane 0 of the env's lane group in a persistent kernel: the
+// autoreset or the step, and the episode contract on the env's EV slots (R envs per workgroup, env r).
+//   * an env whose episode finished resets on the next step: reward 0, not finished, a new episode
+//     from reset number EV_RCOUNT of its Philox stream, the episode counters cleared
+//   * otherwise the step from the env's clipped actions; fin = terminated or truncated (EV_T reached
+//     MAX_STEPS); the step joins the running episode (EV_EPR, EV_EPL), a finished episode the totals
+//     (EV_FR, EV_FL, EV_FC), and EV_AR carries fin to the next step
+// Leaves the state in q and the raw observation in xo (the env's LDS rows). The caller does its own
+// part with the outcome: the rollout's reward and EV_DONE stores, the wrapper chain (term, not fin,
+// goes to NormalizeReward), the evaluation's episode event.
+struct EnvLaneOut {
+  float reward, term;  // term: 1.0f when the step terminated the episode (never on truncation)
+  bool fin, reset;
+  float epr;           // the episode's return and length up to this step (set when !reset)
+  int epl;
+};
+template <int KIND, int R>
+PPO_DEV EnvLaneOut env_lane_step(float* EV, int r, float* q, float* xo, const float* act_row, float lo, float hi) {
+#pragma clang fp contract(off)
+  using D = DevEnv<KIND>;
+  int* EVI = reinterpret_cast<int*>(EV);
+  EnvLaneOut out{0.0f, 0.0f, false, EVI[EV_AR * R + r] != 0, 0.0f, 0};
+  float sreg[D::IN_PLACE ? 1 : D::S], oreg[D::IN_PLACE ? 1 : D::O];
+  float* s = D::IN_PLACE ? q : sreg;
+  float* o = D::IN_PLACE ? xo : oreg;
+  if (out.reset) {
+    const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+    D::reset(rc, rs, s, o);
+    EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+    EVI[EV_T * R + r] = 0;
+    EV[EV_EPR * R + r] = 0.0f;
+    EVI[EV_EPL * R + r] = 0;
+    EVI[EV_AR * R + r] = 0;
+  } else {
+    if constexpr (!D::IN_PLACE) {
+#pragma unroll
+      for (int i = 0; i < D::S; ++i) s[i] = q[i];
+    }
+    float ac[D::A];
+#pragma unroll
+    for (int k = 0; k < D::A; ++k) ac[k] = fminf(fmaxf(act_row[k], lo), hi);
+    out.reward = D::step(s, ac, o, &out.term);
+    const int tt = EVI[EV_T * R + r] + 1;
+    EVI[EV_T * R + r] = tt;
+    out.fin = (out.term != 0.0f) || tt >= D::MAX_STEPS;  // done = terminated or truncated
+    out.epr = (EV[EV_EPR * R + r] + out.reward);
+    EV[EV_EPR * R + r] = out.epr;
+    out.epl = EVI[EV_EPL * R + r] + 1;
+    EVI[EV_EPL * R + r] = out.epl;
+    if (out.fin) {
+      EV[EV_FR * R + r] += out.epr;
+      EV[EV_FL * R + r] += (float)out.epl;
+      EV[EV_FC * R + r] += 1.0f;
+    }
+    EVI[EV_AR * R + r] = out.fin ? 1 : 0;
+  }
+  if constexpr (!D::IN_PLACE) {
+#pragma unroll
+    for (int i = 0; i < D::S; ++i) q[i] = s[i];
+#pragma unroll
+    for (int i = 0; i < D::O; ++i) xo[i] = o[i];
+  }
+  return out;
+}
 
 // staged small parameters of one trunk into LDS (biases, LayerNorm affine, head rows, head biases)
 template <int NHP>

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""AC agent on the device Pendulum-v1 at E = 4096, T = 128 (the metric config's shape): the
-persistent rollout (k_rollout<1, 1, PSYN_PENDULUM> + k_beta_logp + k_values) against the per-step
-path (rollout=per_step: k_act3 + k_pend_step per step), alternating, and the whole iteration
-(rollout + GAE + update). Host clock around work that ends in a device synchronise; both trainers
-are warmed up first. Writes profiles/pendulum/bench_pendulum.txt and .json.
+"""AC agent on one of the device envs with dynamics of their own (Pendulum-v1, CartPoleContinuous-v1,
+ReacherPlanar-v0, QuadrotorHover-v0) at E = 4096, T = 128 (the metric config's shape): the persistent
+rollout (k_rollout<NTO, 1, KIND> + k_beta_logp + k_values) against the per-step path
+(rollout=per_step: k_act3 + k_env_step<KIND> per step), alternating, and the whole iteration
+(rollout + GAE + update). Host clock around work that ends in a device synchronise; both trainers are
+warmed up first. Medians only: no kernel trace is taken. Writes profiles/<name>/bench_<name>.txt and
+.json, <name> being pendulum, cartpole, reacher or quadrotor.
 
-  python scripts/bench_pendulum.py [--num_envs 4096] [--num_steps 128] [--reps 10]
+  python scripts/bench_device_env.py --env_id ID [--num_envs 4096] [--num_steps 128] [--reps 10] [--out DIR]
 """
 import argparse
 import json
@@ -18,16 +20,22 @@ sys.path[:0] = [os.path.join(ROOT, "ppo.cpp_amd"), os.path.join(ROOT, "tests")]
 import numpy as np  # noqa: E402
 import ppo_amd  # noqa: E402
 
+SHORT = {"Pendulum-v1": "pendulum", "CartPoleContinuous-v1": "cartpole", "ReacherPlanar-v0": "reacher",
+         "QuadrotorHover-v0": "quadrotor"}
+
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--env_id", required=True, choices=sorted(SHORT))
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--num_steps", type=int, default=128)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pendulum"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    name = SHORT[a.env_id]
+    out = a.out or os.path.join(ROOT, "profiles", name)
     E, T = a.num_envs, a.num_steps
-    cfg = ppo_amd.ACPPOConfig(env_id="Pendulum-v1", num_envs=E, num_steps=T, total_timesteps=E * T * (4 * a.reps + 8))
+    cfg = ppo_amd.ACPPOConfig(env_id=a.env_id, num_envs=E, num_steps=T, total_timesteps=E * T * (4 * a.reps + 8))
     trs = {"persistent": ppo_amd.Trainer(cfg), "per_step": ppo_amd.Trainer(cfg, options="rollout=per_step")}
     lines = []
 
@@ -35,7 +43,7 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    say(f"AC agent, Pendulum-v1 device env, E={E} T={T}: {E * T} env steps per rollout; {a.reps} alternating repetitions")
+    say(f"AC agent, {a.env_id} device env, E={E} T={T}: {E * T} env steps per rollout; {a.reps} alternating repetitions")
     for tr in trs.values():  # warm-up: code objects, first launches, the update's graph capture
         for _ in range(3):
             tr.iterate()
@@ -75,9 +83,9 @@ def main():
         f"(min {v.min() * 1e3:.3f}, max {v.max() * 1e3:.3f})  {E * T / np.median(v) / 1e6:.2f} M env steps/s")
     for t in trs.values():
         t.close()
-    os.makedirs(a.out, exist_ok=True)
-    open(os.path.join(a.out, "bench_pendulum.txt"), "w").write("\n".join(lines) + "\n")
-    json.dump(res, open(os.path.join(a.out, "bench_pendulum.json"), "w"), indent=1)
+    os.makedirs(out, exist_ok=True)
+    open(os.path.join(out, f"bench_{name}.txt"), "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(os.path.join(out, f"bench_{name}.json"), "w"), indent=1)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 C-ABI: the first device env whose episodes terminate, so episodes end on different steps in different
 envs and the termination flag reaches NormalizeReward.
 
-  1. the per-step device env (k_cart_reset / k_cart_step) is the host env gymcpp/cartpole.h bit for
+  1. the per-step device env (k_env_reset<PSYN_CARTPOLE> / k_env_step<PSYN_CARTPOLE>) is the host env gymcpp/cartpole.h bit for
      bit, without and with the PPO wrapper chain (with it: fails on a kernel that passes te = 0);
   2. the persistent rollouts (k_rollout, k_rollout4 at 4 and at 16 envs per workgroup) are the
      per-step path bit for bit;
@@ -50,7 +50,7 @@ def test_device_env_bitwise_equals_host_env(driver, tmp_path, wrapped):
     actions in [-3, 3], beyond the action space). Without wrappers everything is bitwise; with the PPO
     chain at gamma = 0.99 the normalised observations are within 1 ulp and rewards, dones, episode
     statistics and the wrapper state's reward side are bitwise (test_gpu_wrappers.py's bars). With te
-    forced to 0 in k_cart_step the wrapped case fails at the first step after a termination: the return
+    forced to 0 in k_env_step<PSYN_CARTPOLE> the wrapped case fails at the first step after a termination: the return
     accumulator keeps the finished episode's return."""
     E, T, seed = cc.DESYNC_E, cc.DESYNC_T, cc.DESYNC_SEED
     act = cc.desync_actions()
@@ -139,7 +139,7 @@ def _cu_count():
 
 
 def _advance(tr, steps, seed=21):
-    """`steps` per-step env steps (k_cart_step, through the wrapper chain where attached) with actions
+    """`steps` per-step env steps (k_env_step<PSYN_CARTPOLE>, through the wrapper chain where attached) with actions
     uniform in [-3, 3], into the trainer's next_obs / next_done: the envs are then spread over their
     episodes (lengths 9 .. 71 under such actions), so a short rollout meets terminations."""
     E = tr.hcfg.num_envs
@@ -188,9 +188,9 @@ def _assert_rollouts_equal(trs, iters):
 
 @pytest.mark.parametrize("agent,shape", [("ac", "E37"), ("ppo", "E37"), ("ppo", "4CU+5")])
 def test_persistent_rollout_bitwise_equals_per_step(agent, shape):
-    """AC agent: k_rollout<1, 1, PSYN_CARTPOLE> + k_values vs k_act3 + k_cart_step. PPO agent with the
+    """AC agent: k_rollout<1, 1, PSYN_CARTPOLE> + k_values vs k_act3 + k_env_step<PSYN_CARTPOLE>. PPO agent with the
     wrapper chain: k_rollout4 at 4 envs per workgroup (E = 37) and at 16 (E = 4 CUs + 5: more 4-env
-    workgroups than CUs) vs k_act4 + k_cart_step. Compared: all storage buffers, next_obs / next_done,
+    workgroups than CUs) vs k_act4 + k_env_step<PSYN_CARTPOLE>. Compared: all storage buffers, next_obs / next_done,
     the env state (one more step from it), the wrapper state, the episode statistics and the parameters
     after each update. E = 37, T = 210, 2 iterations: every env finishes several episodes, on its own
     steps, and dones.sum() > E. E = 4 CUs + 5, T = 8, 12 iterations: 96 steps, in which the sampled

@@ -1,6 +1,6 @@
 """Pendulum-v1 on the device (env kind PSYN_PENDULUM, include/ppo_synth_env.h) through the C-ABI.
 
-  1. the per-step device env (k_pend_reset / k_pend_step) is the host env gymcpp/pendulum.h bit for
+  1. the per-step device env (k_env_reset<PSYN_PENDULUM> / k_env_step<PSYN_PENDULUM>) is the host env gymcpp/pendulum.h bit for
      bit, without and with the PPO wrapper chain;
   2. the persistent rollouts (k_rollout, k_rollout4 at 4 and at 16 envs per workgroup) are the
      per-step path bit for bit;
@@ -158,9 +158,9 @@ def _assert_rollouts_equal(trs, iters):
 
 @pytest.mark.parametrize("agent,shape", [("ac", "E37"), ("ppo", "E37"), ("ppo", "4CU+5")])
 def test_persistent_rollout_bitwise_equals_per_step(agent, shape):
-    """AC agent: k_rollout<1, 1, PSYN_PENDULUM> + k_values vs k_act3 + k_pend_step. PPO agent with the
+    """AC agent: k_rollout<1, 1, PSYN_PENDULUM> + k_values vs k_act3 + k_env_step<PSYN_PENDULUM>. PPO agent with the
     wrapper chain: k_rollout4 at 4 envs per workgroup (E = 37) and at 16 (E = 4 CUs + 5: more 4-env
-    workgroups than CUs) vs k_act4 + k_pend_step. T = 210 twice crosses both truncations (steps 200,
+    workgroups than CUs) vs k_act4 + k_env_step<PSYN_PENDULUM>. T = 210 twice crosses both truncations (steps 200,
     401) and starts the second rollout mid-episode."""
     E, T, iters = (37, 210, 2) if shape == "E37" else (4 * _cu_count() + 5, 8, 2)
     C = ppo_amd.ACPPOConfig if agent == "ac" else ppo_amd.PPOConfig

@@ -2,7 +2,7 @@
 C-ABI: the first real task on the two-tile kernels (O = 18, A = 4), a rigid-body quadrotor hovering at
 the origin that terminates (|p|^2 > 9) and truncates (500 steps).
 
-  1. the per-step device env (k_quad_reset / k_quad_step) is the host env gymcpp/quadrotor.h bit for
+  1. the per-step device env (k_env_reset<PSYN_QUADROTOR> / k_env_step<PSYN_QUADROTOR>) is the host env gymcpp/quadrotor.h bit for
      bit over the desynchronised run of test_quadrotor_cpu.py, without and with the PPO wrapper chain
      (with it: against the oracle's chain, as test_gpu_cartpole.py does);
   2. the persistent rollouts (k_rollout<2, 1, PSYN_QUADROTOR>, k_rollout4<2, 1, ., PSYN_QUADROTOR> at 4
@@ -138,7 +138,7 @@ def _cu_count():
 
 
 def _feed(tr, act):
-    """per-step env steps (k_quad_step, through the wrapper chain where attached) with the given
+    """per-step env steps (k_env_step<PSYN_QUADROTOR>, through the wrapper chain where attached) with the given
     actions [steps, E, 4], into the trainer's next_obs / next_done"""
     E = tr.hcfg.num_envs
     rew = DeviceArray(E)
@@ -222,9 +222,9 @@ def _assert_rollout_pair_equal(cfg, opts, T2, update=True, prefix=None):
 
 @pytest.mark.parametrize("agent,shape", [("ac", "E37"), ("ppo", "E37"), ("ppo", "4CU+5")])
 def test_persistent_rollout_bitwise_equals_per_step(agent, shape):
-    """AC agent: k_rollout<2, 1, PSYN_QUADROTOR> + k_values vs k_act3 + k_quad_step. PPO agent with the
+    """AC agent: k_rollout<2, 1, PSYN_QUADROTOR> + k_values vs k_act3 + k_env_step<PSYN_QUADROTOR>. PPO agent with the
     wrapper chain: k_rollout4<2, 1, ., PSYN_QUADROTOR> at 4 envs per workgroup (E = 37) and at 16
-    (E = 4 CUs + 5: more 4-env workgroups than CUs) vs k_act4 + k_quad_step. Two consecutive launches of
+    (E = 4 CUs + 5: more 4-env workgroups than CUs) vs k_act4 + k_env_step<PSYN_QUADROTOR>. Two consecutive launches of
     T = 64: under sampled actions the envs terminate on steps of their own inside them, and an episode
     spans the two launches. Compared: all storage buffers, next_obs / next_done, the env state (the
     steps after), the wrapper state, the episode sums and the parameters after an update. The four

@@ -3,7 +3,7 @@ the first real task with a two-dimensional action (O = 10, A = 2), a two-link pl
 Reacher-v5's task definition over the textbook two-link equations (not MuJoCo's Reacher). Each episode
 has a goal of its own, env state that no step touches and every autoreset redraws.
 
-  1. the per-step device env (k_reach_reset / k_reach_step) is the host env gymcpp/reacher.h bit for
+  1. the per-step device env (k_env_reset<PSYN_REACHER> / k_env_step<PSYN_REACHER>) is the host env gymcpp/reacher.h bit for
      bit, without and with the PPO wrapper chain;
   2. the persistent rollouts (k_rollout, k_rollout4 at 4 and at 16 envs per workgroup) are the
      per-step path bit for bit, over two launches (T = 120, then T = 30 from the state the first left);
@@ -129,7 +129,7 @@ def _cu_count():
 
 
 def _advance(tr, steps, seed=21):
-    """`steps` per-step env steps (k_reach_step, through the wrapper chain where attached) with actions
+    """`steps` per-step env steps (k_env_step<PSYN_REACHER>, through the wrapper chain where attached) with actions
     uniform in [-3, 3]^2, into the trainer's next_obs / next_done."""
     E = tr.hcfg.num_envs
     act = np.random.default_rng(seed).uniform(-3, 3, (steps, E, AD)).astype(np.float32)
@@ -209,9 +209,9 @@ def _assert_rollout_pair_equal(cfg, opts, T2=rc.GPU_T2, update=True):
 
 @pytest.mark.parametrize("agent,shape", [("ac", "E37"), ("ppo", "E37"), ("ppo", "4CU+5")])
 def test_persistent_rollout_bitwise_equals_per_step(agent, shape):
-    """AC agent: k_rollout<1, 1, PSYN_REACHER> + k_values vs k_act3 + k_reach_step. PPO agent with the
+    """AC agent: k_rollout<1, 1, PSYN_REACHER> + k_values vs k_act3 + k_env_step<PSYN_REACHER>. PPO agent with the
     wrapper chain: k_rollout4 at 4 envs per workgroup (E = 37) and at 16 (E = 4 CUs + 5: more 4-env
-    workgroups than CUs) vs k_act4 + k_reach_step. T = 120 holds the autoresets of steps 50 and 101;
+    workgroups than CUs) vs k_act4 + k_env_step<PSYN_REACHER>. T = 120 holds the autoresets of steps 50 and 101;
     the second launch (T = 30) continues the third episode, which ends on the second of the three env
     steps after it. Compared: all storage buffers, next_obs / next_done, the env state (the steps
     after; the goal is part of every observation), the wrapper state, the episode sums and the
