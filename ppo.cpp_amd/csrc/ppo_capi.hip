@@ -654,6 +654,7 @@ extern "C" int ppo_create_ex(const ppo_hip_config* cfg, int device, const char* 
     return -2;
   }
   if (fwdbwd_set_lds(c->K, c->lds_bytes) != 0) {
+    (void)hipGetLastError();  // the refusal is reported here: the next call must not find the attribute call's error
     ppo_destroy(c);
     return fail("ppo_create: cannot set LDS size for the fused update kernel");
   }
