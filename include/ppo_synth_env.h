@@ -5,8 +5,9 @@
  * (libs/gymcpp/mujoco/half_cheetah_v5.h is unbuildable here — no libmujoco) so the GPU path can be
  * measured with inputs resident in HBM. Semantics follow SeqVectorEnv (libs/gymcpp/gym.h:131-163:
  * clip_actions, next-step autoreset with reward 0 / done 0 on the reset step, reset(seed + i))
- * wrapped in RecordEpisodeStatistics (libs/gymcpp/wrappers/common.h:48-65). Dynamics (identical,
- * bit for bit, to the host SyntheticCheetah in ppo.cpp_amd/gymcpp/synthetic/ and oracle/):
+ * wrapped in RecordEpisodeStatistics (libs/gymcpp/wrappers/common.h:48-65). Dynamics (the arithmetic
+ * of include/ppo_cheetah.h, shared with the host SyntheticCheetah of
+ * ppo.cpp_amd/gymcpp/synthetic_cheetah.h; bit for bit also the oracle's own restatement in oracle/):
  *   q'_i = fma(0.9, q_i, fma(0.1, a_{i mod A}, 0.05 * q_{(i+1) mod O}))
  *   r    = (q'_0 - q_0) / 0.05 - sum_k (0.1 a_k) a_k ;  truncation after 1000 steps, never terminates
  *

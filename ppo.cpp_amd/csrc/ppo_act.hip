@@ -93,8 +93,8 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
   if (trunk == 1 && a.mode == PPO_SAMPLE) {
     if constexpr (KIND == PPO_NET_LN_BETA) {
       if (tid < R * A * 2) {
-        const int which = tid & 1, ra = tid >> 1, r = ra / A, ai = ra - r * A;
-        gd0 = gamma_draw(key, a.env_base + row0 + r, a.step_id, 0x10000u + (uint32_t)(ai * 2 + which) * 64u);
+        const BetaItem bi = beta_item(tid, A);
+        gd0 = gamma_draw(key, a.env_base + row0 + bi.r, a.step_id, bi.db);
       }
     } else {
       if (tid < R * A) {
@@ -234,15 +234,13 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
   if constexpr (KIND == PPO_NET_LN_BETA) {
     // stage 1: one (row, action, alpha|beta) item per thread
     for (int idx = tid; idx < R * A * 2; idx += kActThreads) {
-      const int which = idx & 1, ra = idx >> 1, r = ra / A, ai = ra - r * A;
-      const long env = a.env_base + row0 + r;
-      const float c = softplusf_(PRE[r * LDP + ai + which * A]) + 1.0f;
+      const BetaItem bi = beta_item(idx, A);
+      const long env = a.env_base + row0 + bi.r;
+      const float c = softplusf_(PRE[bi.r * LDP + bi.ai + bi.which * A]) + 1.0f;
       float gs = 0.f;
-      if (a.mode == PPO_SAMPLE) {
-        const uint32_t db = 0x10000u + (uint32_t)(ai * 2 + which) * 64u;
-        gs = idx == tid ? gamma_mt_d0(c, gd0, key, env, a.step_id, db) : gamma_mt(c, key, env, a.step_id, db);
-      }
-      float* it = ITM + ((r * A + ai) * 2 + which) * 4;
+      if (a.mode == PPO_SAMPLE)
+        gs = idx == tid ? gamma_mt_d0(c, gd0, key, env, a.step_id, bi.db) : gamma_mt(c, key, env, a.step_id, bi.db);
+      float* it = ITM + ((bi.r * A + bi.ai) * 2 + bi.which) * 4;
       it[0] = c;
       it[1] = gs;
       float tg_unused;
@@ -276,7 +274,7 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
       const float lga = ia[2], lgb = ib[2];
       const float lp = xlogyf_(al - 1.0f, sv) + xlogyf_(be - 1.0f, 1.0f - sv) + (lgab - (lga + lgb));
       const float ent = (lga + lgb) - lgab - (2.0f - ab) * psab - ((al - 1.0f) * ia[3] + (be - 1.0f) * ib[3]);
-      const float act = (sv - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
+      const float act = beta_action(sv, lo, hi);
       LPE[idx * 2 + 0] = lp;
       LPE[idx * 2 + 1] = ent;
       if (valid) {

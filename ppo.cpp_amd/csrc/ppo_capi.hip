@@ -1707,10 +1707,10 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
   return 0;
 }
 
-// the cheetah (no row in kEnvKinds) truncates after 1000 steps and never terminates
+// the cheetah (no row in kEnvKinds) truncates after CHEE_MAX_STEPS steps and never terminates
 static int psyn_max_steps(const psyn_t* env) {
   const EnvKindRow* row = env_kind_row_of(env->a.kind);
-  return row ? row->max_steps : 1000;
+  return row ? row->max_steps : CHEE_MAX_STEPS;
 }
 static bool psyn_terminates(const psyn_t* env) {
   const EnvKindRow* row = env_kind_row_of(env->a.kind);
@@ -1853,7 +1853,7 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
   const bool terminates = psyn_terminates(env);
   const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : (terminates ? 512 : 4096);
   const bool persistent = cfg->mode == 0 && eval_supported(c->K) == 0 && !env->a.w.on;
-  // the env truncates after max_steps (1000; Pendulum 200) steps and resets on the next one: an env
+  // the env truncates after max_steps (the cheetah CHEE_MAX_STEPS, Pendulum 200) steps and resets on the next one: an env
   // finishes at most one episode per max_steps + 1 steps, which bounds the events of a chunk (an
   // overflow is still detected). CartPoleContinuous-v1 and QuadrotorHover-v0 terminate: an episode is
   // at least one step and the reset step after it, so an env finishes at most one episode per 2 steps.

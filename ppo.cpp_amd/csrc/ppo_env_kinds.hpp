@@ -12,10 +12,15 @@
 // Used by the per-step env kernels k_env_reset / k_env_step (ppo_kernels.hip), by env_lane_step
 // (ppo_rollout_common.hpp) inside the persistent kernels k_rollout, k_rollout4 (ppo_rollout.hip) and
 // k_eval (ppo_eval.hip), and by the C API (ppo_capi.hip).
-// PSYN_CHEETAH has no DevEnv: it exists at any (O, A) and its step is spread over an env's lanes.
+// PSYN_CHEETAH has no DevEnv: it exists at any (O, A) and its step is spread over an env's lanes
+// (k_synth_step / k_synth_step_wide, chee_lanes_step of ppo_rollout_common.hpp, k_rollout4's element
+// loop). Its arithmetic is include/ppo_cheetah.h, shared with the host env
+// gymcpp/synthetic_cheetah.h; the device forms of its pieces (chee_reset_elem, chee_clip,
+// chee_reward_clip) are below, next to the reset stream every kind draws from.
 #pragma once
 
 #include "ppo_kernels.hpp"
+#include "../../include/ppo_cheetah.h"
 #include "../../include/ppo_pendulum.h"
 #include "../../include/ppo_cartpole.h"
 #include "../../include/ppo_reacher.h"
@@ -23,16 +28,31 @@
 
 #include <type_traits>
 
-// the uniforms of reset number rc of the env keyed rs: counter (rc, i, 0, 0) for draw i (the
-// cheetah's reset draw of state element i)
+// the uniforms of reset number rc of the env keyed rs: counter (rc, i, 0, 0) for draw i, every kind's
+// reset stream. All kinds share one second key word; the cheetah's header names it (CHEE_RESET_KEY)
+// because the cheetah is the kind whose host env takes it from a shared header, and the host envs of
+// the other kinds (gymcpp/{pendulum,cartpole,reacher,quadrotor}.h) spell the same value themselves.
+constexpr uint32_t kEnvResetKey = CHEE_RESET_KEY;
+PPO_DEV float env_reset_draw(uint32_t rc, uint32_t rs, int i) {
+  uint32_t r[4];
+  philox4x32(rc, (uint32_t)i, 0u, 0u, rs, kEnvResetKey, r);
+  return u01(r[0]);
+}
 template <int N>
 PPO_DEV void env_reset_draws(uint32_t rc, uint32_t rs, float (&u)[N]) {
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    uint32_t r[4];
-    philox4x32(rc, (uint32_t)i, 0u, 0u, rs, 0x5EED5EEDu, r);
-    u[i] = u01(r[0]);
-  }
+  for (int i = 0; i < N; ++i) u[i] = env_reset_draw(rc, rs, i);
+}
+
+// The synthetic cheetah on the device (include/ppo_cheetah.h): state element i of reset number rc,
+// and the reward of a step from the env's unclipped actions ar[0..A-1] (clip_actions applied here, per
+// dimension, as for the element update)
+PPO_DEV float chee_reset_elem(uint32_t rc, uint32_t rs, int i) { return chee_reset_value(env_reset_draw(rc, rs, i)); }
+PPO_DEV float chee_clip(float a, float lo, float hi) { return fminf(fmaxf(a, lo), hi); }
+PPO_DEV float chee_reward_clip(float q0_new, float q0_old, const float* ar, int A, float lo, float hi) {
+  float ctrl = 0.0f;
+  for (int k = 0; k < A; ++k) ctrl = chee_ctrl_add(ctrl, chee_clip(ar[k], lo, hi));
+  return chee_reward_ctrl(q0_new, q0_old, ctrl);
 }
 
 // DevEnv<KIND>:

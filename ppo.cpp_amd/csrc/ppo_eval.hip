@@ -29,7 +29,6 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
   float* NRM = lds + GE::oNRM;
   float* ACT = lds + GE::oACT;
   float* EV = lds + GE::oENV;
-  int* EVI = reinterpret_cast<int*>(EV);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const PackedLayout& K = a.K;
   const float* __restrict__ P = a.P;
@@ -46,23 +45,7 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
     NRM[f] = f < O ? P[K.omean + f] : 0.0f;
     NRM[OP + f] = f < O ? P[K.ostd + f] : 1.0f;
   }
-  for (int idx = tid; idx < R * O; idx += kActThreads) {
-    const int r = idx / O, f = idx - r * O, e = row0 + r;
-    XO[r * LDQ + f] = e < E ? a.obs[(long)e * O + f] : 0.0f;
-    Q[r * LDQ + f] = e < E ? sv.q[(long)e * O + f] : 0.0f;
-  }
-  if (tid < R) {
-    const int e = min(row0 + tid, E - 1);
-    EVI[EV_AR * R + tid] = sv.autoreset[e];
-    EVI[EV_T * R + tid] = sv.t[e];
-    EVI[EV_RSEED * R + tid] = (int)sv.rseed[e];
-    EVI[EV_RCOUNT * R + tid] = (int)sv.rcount[e];
-    EV[EV_EPR * R + tid] = sv.ep_ret[e];
-    EVI[EV_EPL * R + tid] = sv.ep_len[e];
-    EV[EV_FR * R + tid] = sv.fin_ret[e];
-    EV[EV_FL * R + tid] = sv.fin_len[e];
-    EV[EV_FC * R + tid] = sv.fin_cnt[e];
-  }
+  env_slots_load<R, kActThreads>(EV, XO, Q, LDQ, sv, a.obs, nullptr, row0, E, O, tid);
   lds_barrier();
   const SampleKey key = sample_key(a.seed, a.rank);
   const float hi = P[K.hi], lo = P[K.lo];
@@ -86,18 +69,18 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
     GammaDraw gd0 = GammaDraw{0.f, 0.f};
     const auto draw0 = [&] {
       if (sample && bitem < R * A * 2) {
-        const int which = bitem & 1, ra = bitem >> 1, r = ra / A, ai = ra - r * A;
-        gd0 = gamma_draw(key, (long)(row0 + r), step_id, 0x10000u + (uint32_t)(ai * 2 + which) * 64u);
+        const BetaItem bi = beta_item(bitem, A);
+        gd0 = gamma_draw(key, (long)(row0 + bi.r), step_id, bi.db);
       }
     };
     trunk_rows<NTO, NHT>(w1, w2, lds, 2 * A, tid, draw0);
     // ---- concentrations (k_act3 stage 1) and the action on [0, 1] (stage 2) ----
     if (bitem < R * A * 2) {
-      const int which = bitem & 1, ra = bitem >> 1, r = ra / A, ai = ra - r * A;
-      const float c = softplusf_(PRE[r * LDP + ai + which * A]) + 1.0f;
+      const BetaItem bi = beta_item(bitem, A);
+      const float c = softplusf_(PRE[bi.r * LDP + bi.ai + bi.which * A]) + 1.0f;
       float gs = 0.f;
-      if (sample) gs = gamma_mt_d0(c, gd0, key, (long)(row0 + r), step_id, 0x10000u + (uint32_t)(ai * 2 + which) * 64u);
-      float* it = ITM + ((r * A + ai) * 2 + which) * 4;
+      if (sample) gs = gamma_mt_d0(c, gd0, key, (long)(row0 + bi.r), step_id, bi.db);
+      float* it = ITM + ((bi.r * A + bi.ai) * 2 + bi.which) * 4;
       it[0] = c;
       it[1] = gs;
     }
@@ -111,120 +94,27 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
       if (a.mode == PPO_MEAN) s01 = al / (al + be);
       else if (a.mode == PPO_ROACH) s01 = beta_roach01(al, be);
       else s01 = beta_sample01(ia[1], ib[1]);
-      ACT[r * 24 + ai] = (s01 - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
+      ACT[r * 24 + ai] = beta_action(s01, lo, hi);
     }
     lds_barrier();
-    // ---- env step: 32 lanes per env; a finished episode is one event ----
-    if constexpr (KIND != PSYN_CHEETAH) {
-      // a kind with a DevEnv (k_env_step arithmetic): lane 0 of each env's lane group steps the env
-      // from its actions ACT[r * 24 + 0..A-1]; an episode that terminates or is truncated, on whatever
-      // step, is one event
-#pragma clang fp contract(off)
+    // ---- env step: 32 lanes per env (k_rollout's); an episode that terminates or is truncated, on
+    // whatever step, is one event ----
+    {
       const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        const EnvLaneOut o = env_lane_step<KIND, R>(EV, r, Q + r * LDQ, XO + r * LDQ, ACT + r * 24, a.lo, a.hi);
-        if (o.fin) {
-          const unsigned slot = atomicAdd(a.count, 1u);
-          if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, o.epl, o.epr};
-        }
-      }
-    } else {
-      // the synthetic cheetah (k_synth_step arithmetic)
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      const bool live = e < E;
-      const bool reset = EVI[EV_AR * R + r] != 0;
-      float* q = Q + r * LDQ;
-      float* xo = XO + r * LDQ;
-      const float* ar = ACT + r * 24;
-      if (live && reset) {
-        const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          if (i < O) {
-            uint32_t rr[4];
-            philox4x32(rc, (uint32_t)i, 0u, 0u, rs, 0x5EED5EEDu, rr);
-            const float v = (0.1f * ((2.0f * u01(rr[0])) - 1.0f));
-            q[i] = v;
-            xo[i] = v;
-          }
-        }
-        if (i0 == 0) {
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EVI[EV_AR * R + r] = 0;
-        }
-      } else if (live) {
-        float qo[NCH], qn[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          qo[c] = i < O ? q[i] : 0.0f;
-          qn[c] = i < O ? q[i + 1 < O ? i + 1 : 0] : 0.0f;
-        }
-        float q0_new = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          if (i < O) {
-            const float ai = fminf(fmaxf(ar[i % A], a.lo), a.hi);
-            const float nq = __fmaf_rn(0.9f, qo[c], __fmaf_rn(0.1f, ai, (0.05f * qn[c])));
-            q[i] = nq;
-            xo[i] = nq;
-            if (c == 0) q0_new = nq;
-          }
-        }
-        if (i0 == 0) {
-          const float vel = ((q0_new - qo[0]) / 0.05f);
-          float ctrl = 0.0f;
-          for (int k = 0; k < A; ++k) {
-            const float ak = fminf(fmaxf(ar[k], a.lo), a.hi);
-            ctrl = (ctrl + ((0.1f * ak) * ak));
-          }
-          const float rw = (vel - ctrl);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= 1000;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-            const unsigned slot = atomicAdd(a.count, 1u);
-            if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, epl, epr};
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
+      if (e < E) {
+        env_lanes_step<KIND, R, NCH>(EV, r, i0, O, A, Q + r * LDQ, XO + r * LDQ, ACT + r * 24, a.lo, a.hi,
+                                     [&](const EnvLaneOut& o) {
+                                       if (o.fin) {
+                                         const unsigned slot = atomicAdd(a.count, 1u);
+                                         if (slot < (unsigned)a.cap) a.ev[slot] = EvalEvent{a.k0 + t, e, o.epl, o.epr};
+                                       }
+                                     });
       }
     }
     lds_barrier();
   }
   // ---- epilogue: the obs and the env state back to HBM (the next chunk continues from them) ----
-  for (int idx = tid; idx < R * O; idx += kActThreads) {
-    const int r = idx / O, f = idx - r * O, e = row0 + r;
-    if (e < E) {
-      a.obs[(long)e * O + f] = XO[r * LDQ + f];
-      sv.q[(long)e * O + f] = Q[r * LDQ + f];
-    }
-  }
-  if (tid < R && row0 + tid < E) {
-    const int e = row0 + tid;
-    sv.autoreset[e] = EVI[EV_AR * R + tid];
-    sv.t[e] = EVI[EV_T * R + tid];
-    sv.rseed[e] = (uint32_t)EVI[EV_RSEED * R + tid];
-    sv.rcount[e] = (uint32_t)EVI[EV_RCOUNT * R + tid];
-    sv.ep_ret[e] = EV[EV_EPR * R + tid];
-    sv.ep_len[e] = EVI[EV_EPL * R + tid];
-    sv.fin_ret[e] = EV[EV_FR * R + tid];
-    sv.fin_len[e] = EV[EV_FL * R + tid];
-    sv.fin_cnt[e] = EV[EV_FC * R + tid];
-  }
+  env_slots_store<R, kActThreads>(EV, XO, Q, LDQ, sv, a.obs, nullptr, row0, E, O, tid);
 }
 
 // the per-step path's recorder, after psyn_step of evaluation step `step`: an env whose step ended

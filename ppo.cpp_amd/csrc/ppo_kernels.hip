@@ -2248,36 +2248,60 @@ __global__ __launch_bounds__(256) void k_wrap_step(WrapArgs w, int O, int e0, in
   if (reward && !(is_reset && is_reset[e] != 0.0f)) reward[e] = wrap_reward(w, e, reward[e], term ? term[e] : 0.0f);
 }
 
-PPO_DEV void synth_reset_one(SynthArgs& a, int e, int seed, float* obs) {
-#pragma clang fp contract(off)
-  if (seed > 0) { a.rseed[e] = (uint32_t)seed; a.rcount[e] = 0; }
-  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
-  for (int i = 0; i < a.O; ++i) {
-    uint32_t r[4];
-    philox4x32(rc, (uint32_t)i, 0u, 0u, rs, 0x5EED5EEDu, r);
-    const float q = (0.1f * ((2.0f * u01(r[0])) - 1.0f));
-    a.q[(long)e * a.O + i] = q;
-    obs[(long)e * a.O + i] = a.w.on ? wrap_obs_dim(a.w, e, a.O, i, oc, q) : q;
-  }
-  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
+// The episode contract of the vector env on SynthArgs' per-env arrays, by the one lane that owns env e
+// in a per-step kernel (the persistent kernels keep the same contract on their LDS slots:
+// ev_autoreset / ev_step_account, ppo_rollout_common.hpp):
+//   * a new episode, at a reset or at the autoreset of the step after an episode finished, after the
+//     draws of reset number rc: the episode counters cleared (an autoreset step also reports reward 0
+//     and done 0 itself)
+//   * a step with reward r and termination flag te: done = terminated or truncated (t reached
+//     max_steps); the reward goes out through NormalizeReward (te, not done, restarts its return), the
+//     step joins the running episode, a finished episode the totals, and autoreset carries done to the
+//     next step
+PPO_DEV void synth_episode_begin(const SynthArgs& a, int e, uint32_t rc) {
   a.rcount[e] = rc + 1;
   a.t[e] = 0;
   a.ep_ret[e] = 0.0f;
   a.ep_len[e] = 0;
+  a.autoreset[e] = 0;
+}
+PPO_DEV void synth_step_account(const SynthArgs& a, int e, float r, float te, int max_steps, float* __restrict__ reward,
+                                float* __restrict__ done) {
+#pragma clang fp contract(off)
+  const int t = a.t[e] + 1;
+  a.t[e] = t;
+  const bool fin = (te != 0.0f) || t >= max_steps;
+  reward[e] = a.w.on ? wrap_reward(a.w, e, r, te) : r;
+  done[e] = fin ? 1.0f : 0.0f;
+  a.ep_ret[e] = (a.ep_ret[e] + r);
+  a.ep_len[e] += 1;
+  if (fin) {
+    a.fin_ret[e] += a.ep_ret[e];
+    a.fin_len[e] += (float)a.ep_len[e];
+    a.fin_cnt[e] += 1.0f;
+  }
+  a.autoreset[e] = fin ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void k_synth_reset(SynthArgs a, int seed, float* obs, float* done) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.E) return;
-  synth_reset_one(a, e, seed + e, obs);
-  a.autoreset[e] = 0;
+  if (seed + e > 0) { a.rseed[e] = (uint32_t)(seed + e); a.rcount[e] = 0; }
+  const uint32_t rs = a.rseed[e], rc = a.rcount[e];
+  const float oc = a.w.on ? a.w.ocount[e] : 0.0f;
+  for (int i = 0; i < a.O; ++i) {
+    const float q = chee_reset_elem(rc, rs, i);
+    a.q[(long)e * a.O + i] = q;
+    obs[(long)e * a.O + i] = a.w.on ? wrap_obs_dim(a.w, e, a.O, i, oc, q) : q;
+  }
+  if (a.w.on) a.w.ocount[e] = oc + 1.0f;
+  synth_episode_begin(a, e, rc);
   if (done) done[e] = 0.0f;
 }
 
 // One thread per (env, observation dim): 32 lanes per env (2 envs per wave), q_(i+1) comes from the
 // neighbouring lane, so all reads of the old state happen before any write; lane 0 of each env does
-// the per-env reward / time limit / episode statistics. Same fp32 ops as synth_reset_one and the
+// the per-env reward / time limit / episode statistics. Same fp32 ops as k_synth_reset and the
 // oracle (no contraction): bit-exact.
 __global__ __launch_bounds__(256) void k_synth_step(SynthArgs a, int e0, int e1, const float* __restrict__ act,
                                                     float lo, float hi, float* __restrict__ obs,
@@ -2299,50 +2323,24 @@ __global__ __launch_bounds__(256) void k_synth_step(SynthArgs a, int e0, int e1,
   const float oc = a.w.on ? a.w.ocount[e] : 0.0f;  // read by every lane before lane 0 stores oc + 1
   if (reset) {
     const uint32_t rs = a.rseed[e], rc = a.rcount[e];
-    uint32_t r[4];
-    philox4x32(rc, (uint32_t)i, 0u, 0u, rs, 0x5EED5EEDu, r);
-    const float v = (0.1f * ((2.0f * u01(r[0])) - 1.0f));
+    const float v = chee_reset_elem(rc, rs, i);
     q[i] = v;
     obs[(long)e * O + i] = a.w.on ? wrap_obs_dim(a.w, e, O, i, oc, v) : v;
     if (i == 0) {
       if (a.w.on) a.w.ocount[e] = oc + 1.0f;
-      a.rcount[e] = rc + 1;
-      a.t[e] = 0;
-      a.ep_ret[e] = 0.0f;
-      a.ep_len[e] = 0;
+      synth_episode_begin(a, e, rc);
       reward[e] = 0.0f;
       done[e] = 0.0f;
-      a.autoreset[e] = 0;
     }
     return;
   }
-  // q'_i = 0.9 q_i + (0.1 a_(i mod A) + 0.05 q_(i+1 mod O))  (fmaf, no contraction)
-  const float ai = fminf(fmaxf(ar[i % A], lo), hi);
-  const float nq = __fmaf_rn(0.9f, qi, __fmaf_rn(0.1f, ai, (0.05f * qn)));
+  const float nq = chee_next_q(qi, chee_clip(ar[i % A], lo, hi), qn);
   q[i] = nq;
   obs[(long)e * O + i] = a.w.on ? wrap_obs_dim(a.w, e, O, i, oc, nq) : nq;
   if (i != 0) return;
   if (a.w.on) a.w.ocount[e] = oc + 1.0f;
-  const float vel = ((nq - qi) / 0.05f);
-  float ctrl = 0.0f;
-  for (int k = 0; k < A; ++k) {
-    const float ak = fminf(fmaxf(ar[k], lo), hi);
-    ctrl = (ctrl + ((0.1f * ak) * ak));
-  }
-  const float r = (vel - ctrl);
-  const int t = a.t[e] + 1;
-  a.t[e] = t;
-  const bool tr = t >= 1000;
-  reward[e] = a.w.on ? wrap_reward(a.w, e, r, 0.0f) : r;  // the synthetic env never terminates
-  done[e] = tr ? 1.0f : 0.0f;
-  a.ep_ret[e] = (a.ep_ret[e] + r);
-  a.ep_len[e] += 1;
-  if (tr) {
-    a.fin_ret[e] += a.ep_ret[e];
-    a.fin_len[e] += (float)a.ep_len[e];
-    a.fin_cnt[e] += 1.0f;
-  }
-  a.autoreset[e] = tr ? 1 : 0;
+  // the synthetic env never terminates
+  synth_step_account(a, e, chee_reward_clip(nq, qi, ar, A, lo, hi), 0.0f, CHEE_MAX_STEPS, reward, done);
 }
 
 // Wide observations (32 < O <= 64 * kSynthWideChunks, e.g. Ant 105, Humanoid 376): one wave per
@@ -2373,22 +2371,16 @@ __global__ __launch_bounds__(256) void k_synth_step_wide(SynthArgs a, int e0, in
     for (int c = 0; c < kSynthWideChunks; ++c) {
       const int i = 64 * c + lane;
       if (i < O) {
-        uint32_t r[4];
-        philox4x32(rc, (uint32_t)i, 0u, 0u, rs, 0x5EED5EEDu, r);
-        const float v = (0.1f * ((2.0f * u01(r[0])) - 1.0f));
+        const float v = chee_reset_elem(rc, rs, i);
         q[i] = v;
         obs[(long)e * O + i] = a.w.on ? wrap_obs_dim(a.w, e, O, i, oc, v) : v;
       }
     }
     if (lane == 0) {
       if (a.w.on) a.w.ocount[e] = oc + 1.0f;
-      a.rcount[e] = rc + 1;
-      a.t[e] = 0;
-      a.ep_ret[e] = 0.0f;
-      a.ep_len[e] = 0;
+      synth_episode_begin(a, e, rc);
       reward[e] = 0.0f;
       done[e] = 0.0f;
-      a.autoreset[e] = 0;
     }
     return;
   }
@@ -2402,8 +2394,7 @@ __global__ __launch_bounds__(256) void k_synth_step_wide(SynthArgs a, int e0, in
     const int i = 64 * c + lane;
     const float qn = (i + 1 == O) ? q0 : (lane < 63 ? up : nxt);
     if (i < O) {
-      const float ai = fminf(fmaxf(ar[i % A], lo), hi);
-      const float nq = __fmaf_rn(0.9f, qv[c], __fmaf_rn(0.1f, ai, (0.05f * qn)));
+      const float nq = chee_next_q(qv[c], chee_clip(ar[i % A], lo, hi), qn);
       q[i] = nq;
       obs[(long)e * O + i] = a.w.on ? wrap_obs_dim(a.w, e, O, i, oc, nq) : nq;
       if (i == 0) { q0_new = nq; q0_old = qv[c]; }
@@ -2411,26 +2402,7 @@ __global__ __launch_bounds__(256) void k_synth_step_wide(SynthArgs a, int e0, in
   }
   if (lane != 0) return;
   if (a.w.on) a.w.ocount[e] = oc + 1.0f;
-  const float vel = ((q0_new - q0_old) / 0.05f);
-  float ctrl = 0.0f;
-  for (int k = 0; k < A; ++k) {
-    const float ak = fminf(fmaxf(ar[k], lo), hi);
-    ctrl = (ctrl + ((0.1f * ak) * ak));
-  }
-  const float r = (vel - ctrl);
-  const int t = a.t[e] + 1;
-  a.t[e] = t;
-  const bool tr = t >= 1000;
-  reward[e] = a.w.on ? wrap_reward(a.w, e, r, 0.0f) : r;  // the synthetic env never terminates
-  done[e] = tr ? 1.0f : 0.0f;
-  a.ep_ret[e] = (a.ep_ret[e] + r);
-  a.ep_len[e] += 1;
-  if (tr) {
-    a.fin_ret[e] += a.ep_ret[e];
-    a.fin_len[e] += (float)a.ep_len[e];
-    a.fin_cnt[e] += 1.0f;
-  }
-  a.autoreset[e] = tr ? 1 : 0;
+  synth_step_account(a, e, chee_reward_clip(q0_new, q0_old, ar, A, lo, hi), 0.0f, CHEE_MAX_STEPS, reward, done);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2460,11 +2432,7 @@ __global__ __launch_bounds__(256) void k_env_reset(SynthArgs a, int seed, float*
   float* q = a.q + (long)e * D::O;
   for (int i = 0; i < D::S; ++i) q[i] = s[i];  // the slots S..O-1 are zero from creation on
   env_store_obs<D::O>(a, e, a.w.on ? a.w.ocount[e] : 0.0f, o, obs);
-  a.rcount[e] = rc + 1;
-  a.t[e] = 0;
-  a.ep_ret[e] = 0.0f;
-  a.ep_len[e] = 0;
-  a.autoreset[e] = 0;
+  synth_episode_begin(a, e, rc);
   if (done) done[e] = 0.0f;
 }
 
@@ -2484,13 +2452,9 @@ __global__ __launch_bounds__(256) void k_env_step(SynthArgs a, int e0, int e1, c
     D::reset(rc, rs, s, o);
     for (int i = 0; i < D::S; ++i) q[i] = s[i];
     env_store_obs<D::O>(a, e, oc, o, obs);
-    a.rcount[e] = rc + 1;
-    a.t[e] = 0;
-    a.ep_ret[e] = 0.0f;
-    a.ep_len[e] = 0;
+    synth_episode_begin(a, e, rc);
     reward[e] = 0.0f;
     done[e] = 0.0f;
-    a.autoreset[e] = 0;
     return;
   }
   for (int i = 0; i < D::S; ++i) s[i] = q[i];
@@ -2501,19 +2465,7 @@ __global__ __launch_bounds__(256) void k_env_step(SynthArgs a, int e0, int e1, c
   const float r = D::step(s, ac, o, &te);
   for (int i = 0; i < D::S; ++i) q[i] = s[i];
   env_store_obs<D::O>(a, e, oc, o, obs);
-  const int t = a.t[e] + 1;
-  a.t[e] = t;
-  const bool fin = (te != 0.0f) || t >= D::MAX_STEPS;  // done = terminated or truncated
-  reward[e] = a.w.on ? wrap_reward(a.w, e, r, te) : r;
-  done[e] = fin ? 1.0f : 0.0f;
-  a.ep_ret[e] = (a.ep_ret[e] + r);
-  a.ep_len[e] += 1;
-  if (fin) {
-    a.fin_ret[e] += a.ep_ret[e];
-    a.fin_len[e] += (float)a.ep_len[e];
-    a.fin_cnt[e] += 1.0f;
-  }
-  a.autoreset[e] = fin ? 1 : 0;
+  synth_step_account(a, e, r, te, D::MAX_STEPS, reward, done);
 }
 
 // =============================================================================================

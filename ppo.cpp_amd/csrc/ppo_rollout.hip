@@ -78,7 +78,6 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
   float* NRM = lds + GE::oNRM;
   float* ACT = lds + GE::oACT;
   float* EV = lds + GE::oENV;
-  int* EVI = reinterpret_cast<int*>(EV);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const PackedLayout& K = a.K;
   const float* __restrict__ P = a.P;
@@ -95,24 +94,7 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
     NRM[f] = f < O ? P[K.omean + f] : 0.0f;
     NRM[OP + f] = f < O ? P[K.ostd + f] : 1.0f;
   }
-  for (int idx = tid; idx < R * O; idx += kActThreads) {
-    const int r = idx / O, f = idx - r * O, e = row0 + r;
-    XO[r * LDQ + f] = e < E ? a.next_obs[(long)e * O + f] : 0.0f;
-    Q[r * LDQ + f] = e < E ? sv.q[(long)e * O + f] : 0.0f;
-  }
-  if (tid < R) {
-    const int e = min(row0 + tid, E - 1);
-    EV[EV_DONE * R + tid] = a.next_done[e];
-    EVI[EV_AR * R + tid] = sv.autoreset[e];
-    EVI[EV_T * R + tid] = sv.t[e];
-    EVI[EV_RSEED * R + tid] = (int)sv.rseed[e];
-    EVI[EV_RCOUNT * R + tid] = (int)sv.rcount[e];
-    EV[EV_EPR * R + tid] = sv.ep_ret[e];
-    EVI[EV_EPL * R + tid] = sv.ep_len[e];
-    EV[EV_FR * R + tid] = sv.fin_ret[e];
-    EV[EV_FL * R + tid] = sv.fin_len[e];
-    EV[EV_FC * R + tid] = sv.fin_cnt[e];
-  }
+  env_slots_load<R, kActThreads>(EV, XO, Q, LDQ, sv, a.next_obs, a.next_done, row0, E, O, tid);
   lds_barrier();
   const SampleKey key = sample_key(a.seed, a.rank);
   const float hi = P[K.hi], lo = P[K.lo];
@@ -145,9 +127,8 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
     // LDS pass and one barrier fewer per step
     const auto draw0 = [&] {
       if (bitem < R * A * 2) {
-        const int which = bitem & 1, ra = bitem >> 1, r = ra / A, ai = ra - r * A;
-        const uint32_t db = 0x10000u + (uint32_t)(ai * 2 + which) * 64u;
-        gd0 = gamma_draw(key, (long)(row0 + r), step_id, db);
+        const BetaItem bi = beta_item(bitem, A);
+        gd0 = gamma_draw(key, (long)(row0 + bi.r), step_id, bi.db);
       }
     };
     if (defer) trunk_rows<NTO, NHT, 1, false>(w1, w2, lds, 2 * A, tid, draw0, (int)t);
@@ -156,7 +137,8 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
     // or, with a.s_beta, stored for k_beta_logp after the rollout (they are not on the env's path) ----
     ROLL_STAMP(t, 2);
     if (bitem < R * A * 2) {
-      const int idx = bitem, which = idx & 1, ra = idx >> 1, r = ra / A, ai = ra - r * A;
+      const BetaItem bi = beta_item(bitem, A);
+      const int which = bi.which, r = bi.r, ai = bi.ai;
       const long env = row0 + r;
       float pre;
       if (defer) {
@@ -173,8 +155,7 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
       if (t == 0 && env == kRdbgEnv) RDBG(0, 1160 + ai + which * A, pre);
 #endif
       const float c = softplusf_(pre) + 1.0f;
-      const uint32_t db = 0x10000u + (uint32_t)(ai * 2 + which) * 64u;
-      const float gs = gamma_mt_d0(c, gd0, key, env, step_id, db);
+      const float gs = gamma_mt_d0(c, gd0, key, env, step_id, bi.db);
       float* it = ITM + ((r * A + ai) * 2 + which) * 4;
       it[0] = c;
       it[1] = gs;
@@ -190,7 +171,7 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
       const float* ib = ITM + (idx * 2 + 1) * 4;
       const float al = ia[0], be = ib[0];
       const float s01 = beta_sample01(ia[1], ib[1]);
-      const float act = (s01 - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
+      const float act = beta_action(s01, lo, hi);
       ACT[r * 24 + ai] = act;
       if (e < E) a.s_actions[((long)t * E + e) * A + ai] = act;
       if (defer) {
@@ -215,119 +196,25 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
       a.s_logp[(long)t * E + row0 + tid] = lp;
     }
     ROLL_STAMP(t, 3);
-    // ---- env step: 32 lanes per env ----
-    if constexpr (KIND != PSYN_CHEETAH) {
-      // a kind with a DevEnv (k_env_step arithmetic): lane 0 of each env's lane group steps the env
-      // from its actions ACT[r * 24 + 0..A-1] (written by other lanes before the barrier above). No
-      // wrapper chain in this kernel: the termination flag feeds done only.
-#pragma clang fp contract(off)
+    // ---- env step: 32 lanes per env (the cheetah: k_synth_step / k_synth_step_wide arithmetic over
+    // them; a kind with a DevEnv: k_env_step arithmetic on lane 0, from the actions other lanes wrote to
+    // ACT before the barrier above). No wrapper chain in this kernel: the termination flag feeds done
+    // only. ----
+    {
       const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      if (i0 == 0 && e < E) {
-        const EnvLaneOut o = env_lane_step<KIND, R>(EV, r, Q + r * LDQ, XO + r * LDQ, ACT + r * 24, a.lo, a.hi);
-        a.s_rewards[(long)t * E + e] = o.reward;
-        EV[EV_DONE * R + r] = o.fin ? 1.0f : 0.0f;
-      }
-    } else {
-      // the synthetic cheetah (k_synth_step / k_synth_step_wide arithmetic)
-#pragma clang fp contract(off)
-      const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      const bool live = e < E;
-      const bool reset = EVI[EV_AR * R + r] != 0;
-      float* q = Q + r * LDQ;
-      float* xo = XO + r * LDQ;
-      const float* ar = ACT + r * 24;
-      if (live && reset) {
-        const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          if (i < O) {
-            uint32_t rr[4];
-            philox4x32(rc, (uint32_t)i, 0u, 0u, rs, 0x5EED5EEDu, rr);
-            const float v = (0.1f * ((2.0f * u01(rr[0])) - 1.0f));
-            q[i] = v;
-            xo[i] = v;
-          }
-        }
-        if (i0 == 0) {
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        }
-      } else if (live) {
-        float qo[NCH], qn[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          qo[c] = i < O ? q[i] : 0.0f;
-          qn[c] = i < O ? q[i + 1 < O ? i + 1 : 0] : 0.0f;
-        }
-        float q0_new = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          if (i < O) {
-            const float ai = fminf(fmaxf(ar[i % A], a.lo), a.hi);
-            const float nq = __fmaf_rn(0.9f, qo[c], __fmaf_rn(0.1f, ai, (0.05f * qn[c])));
-            q[i] = nq;
-            xo[i] = nq;
-            if (c == 0) q0_new = nq;
-          }
-        }
-        if (i0 == 0) {
-          const float vel = ((q0_new - qo[0]) / 0.05f);
-          float ctrl = 0.0f;
-          for (int k = 0; k < A; ++k) {
-            const float ak = fminf(fmaxf(ar[k], a.lo), a.hi);
-            ctrl = (ctrl + ((0.1f * ak) * ak));
-          }
-          const float rw = (vel - ctrl);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= 1000;
-          a.s_rewards[(long)t * E + e] = rw;
-          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
+      if (e < E) {
+        env_lanes_step<KIND, R, NCH>(EV, r, i0, O, A, Q + r * LDQ, XO + r * LDQ, ACT + r * 24, a.lo, a.hi,
+                                     [&](const EnvLaneOut& o) {
+                                       a.s_rewards[(long)t * E + e] = o.reward;
+                                       EV[EV_DONE * R + r] = o.fin ? 1.0f : 0.0f;
+                                     });
       }
     }
     lds_barrier();
     ROLL_STAMP(t, 4);
   }
   // ---- epilogue: next_obs / next_done and the env state back to HBM ----
-  for (int idx = tid; idx < R * O; idx += kActThreads) {
-    const int r = idx / O, f = idx - r * O, e = row0 + r;
-    if (e < E) {
-      a.next_obs[(long)e * O + f] = XO[r * LDQ + f];
-      sv.q[(long)e * O + f] = Q[r * LDQ + f];
-    }
-  }
-  if (tid < R && row0 + tid < E) {
-    const int e = row0 + tid;
-    a.next_done[e] = EV[EV_DONE * R + tid];
-    sv.autoreset[e] = EVI[EV_AR * R + tid];
-    sv.t[e] = EVI[EV_T * R + tid];
-    sv.rseed[e] = (uint32_t)EVI[EV_RSEED * R + tid];
-    sv.rcount[e] = (uint32_t)EVI[EV_RCOUNT * R + tid];
-    sv.ep_ret[e] = EV[EV_EPR * R + tid];
-    sv.ep_len[e] = EVI[EV_EPL * R + tid];
-    sv.fin_ret[e] = EV[EV_FR * R + tid];
-    sv.fin_len[e] = EV[EV_FL * R + tid];
-    sv.fin_cnt[e] = EV[EV_FC * R + tid];
-  }
+  env_slots_store<R, kActThreads>(EV, XO, Q, LDQ, sv, a.next_obs, a.next_done, row0, E, O, tid);
 }
 
 // =============================================================================================
@@ -698,7 +585,8 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
         }
       }
     } else {
-      // the synthetic cheetah (k_synth_step / _wide arithmetic)
+      // the synthetic cheetah (k_synth_step / _wide arithmetic) over the env's LPE lanes; lane 0 does
+      // the reward and the episode contract (chee_lanes_step's, with the wrapper chain in between)
 #pragma clang fp contract(off)
       const int r = tid / LPE, i0 = tid % LPE, e = row0 + r;
       if (e < E) {
@@ -715,9 +603,7 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
           for (int c = 0; c < NCE; ++c) {
             const int i = LPE * c + i0;
             if (i < O) {
-              uint32_t rr[4];
-              philox4x32(rc, (uint32_t)i, 0u, 0u, rs, 0x5EED5EEDu, rr);
-              const float v = (0.1f * ((2.0f * u01(rr[0])) - 1.0f));
+              const float v = chee_reset_elem(rc, rs, i);
               q[i] = v;
               xo[i] = w.on ? wrap_obs_at(om + i, ov + i, oc, v) : v;
             }
@@ -765,8 +651,7 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
 #pragma unroll
             for (int u = 0; u < kEnvGroup; ++u) {
               if (c0 + u < NCE) {
-                const float aic = fminf(fmaxf(ac[u], a.lo), a.hi);
-                nq[u] = __fmaf_rn(0.9f, qo[u], __fmaf_rn(0.1f, aic, (0.05f * qn[u])));
+                nq[u] = chee_next_q(qo[u], chee_clip(ac[u], a.lo, a.hi), qn[u]);
                 xn[u] = w.on ? wrap_obs_at_r(&wm[u], &wv[u], oc, rtot, nq[u]) : nq[u];
               }
             }
@@ -786,16 +671,10 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
           }
           if (i0 == 0) {
             if (w.on) EV[EV_WOC * R + r] = oc + 1.0f;
-            const float vel = ((q0_new - q0_old) / 0.05f);
-            float ctrl = 0.0f;
-            for (int k = 0; k < A; ++k) {
-              const float ak = fminf(fmaxf(ar[k], a.lo), a.hi);
-              ctrl = (ctrl + ((0.1f * ak) * ak));
-            }
-            const float rw = (vel - ctrl);
+            const float rw = chee_reward_clip(q0_new, q0_old, ar, A, a.lo, a.hi);
             const int tt = EVI[EV_T * R + r] + 1;
             EVI[EV_T * R + r] = tt;
-            const bool tr = tt >= 1000;
+            const bool tr = tt >= CHEE_MAX_STEPS;
             a.s_rewards[(long)t * E + e] =
                 w.on ? wrap_reward_at(EV + EV_WRA * R + r, EV + EV_WRM * R + r, EV + EV_WRV * R + r,
                                       EV + EV_WRC * R + r, w.gamma, rw, 0.0f)
@@ -990,7 +869,6 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
   float* NRM = lds + GE::oNRM;
   float* ACT = lds + GE::oACT;
   float* EV = lds + GE::oENV;
-  int* EVI = reinterpret_cast<int*>(EV);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rg = wave >> 2, f = 64 * (wave & 3) + lane;  // this lane's row and output feature
@@ -1039,24 +917,7 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
     NRM[i] = i < O ? P[K.omean + i] : 0.0f;
     NRM[OP + i] = i < O ? P[K.ostd + i] : 1.0f;
   }
-  for (int idx = tid; idx < R * O; idx += kRVThreads) {
-    const int r = idx / O, ff = idx - r * O, e = row0 + r;
-    XO[r * LDQ + ff] = e < E ? a.next_obs[(long)e * O + ff] : 0.0f;
-    Q[r * LDQ + ff] = e < E ? sv.q[(long)e * O + ff] : 0.0f;
-  }
-  if (tid < R) {
-    const int e = min(row0 + tid, E - 1);
-    EV[EV_DONE * R + tid] = a.next_done[e];
-    EVI[EV_AR * R + tid] = sv.autoreset[e];
-    EVI[EV_T * R + tid] = sv.t[e];
-    EVI[EV_RSEED * R + tid] = (int)sv.rseed[e];
-    EVI[EV_RCOUNT * R + tid] = (int)sv.rcount[e];
-    EV[EV_EPR * R + tid] = sv.ep_ret[e];
-    EVI[EV_EPL * R + tid] = sv.ep_len[e];
-    EV[EV_FR * R + tid] = sv.fin_ret[e];
-    EV[EV_FL * R + tid] = sv.fin_len[e];
-    EV[EV_FC * R + tid] = sv.fin_cnt[e];
-  }
+  env_slots_load<R, kRVThreads>(EV, XO, Q, LDQ, sv, a.next_obs, a.next_done, row0, E, O, tid);
   lds_barrier();
   const SampleKey key = sample_key(a.seed, a.rank);
   const float hi = P[K.hi], lo = P[K.lo];
@@ -1068,8 +929,8 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
   auto draw0 = [&](long step) {
     GammaDraw d = GammaDraw{0.f, 0.f};
     if (bitem < R * A * 2) {
-      const int which = bitem & 1, ra = bitem >> 1, r = ra / A, ai = ra - r * A;
-      d = gamma_draw(key, (long)(row0 + r), step, 0x10000u + (uint32_t)(ai * 2 + which) * 64u);
+      const BetaItem bi = beta_item(bitem, A);
+      d = gamma_draw(key, (long)(row0 + bi.r), step, bi.db);
     }
     return d;
   };
@@ -1236,7 +1097,8 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
     // (quad xor 1) instead of a round trip through LDS and a barrier ----
     float bc = 1.0f, bg = 1.0f;
     if (bitem < R * A * 2) {
-      const int which = bitem & 1, ra = bitem >> 1, r = ra / A, ai = ra - r * A, h = ai + which * A;
+      const BetaItem bi = beta_item(bitem, A);
+      const int r = bi.r, h = bi.ai + bi.which * A;
       float sm = 0.f;
 #pragma unroll
       for (int w = 0; w < kActWaves; ++w) sm += HP[(w * NHP + h) * R + r];
@@ -1244,8 +1106,7 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
 #ifdef PPO_STAMPS
       if (t == 0 && kRdbgEnv == row0 + r) RDBG(1, 1160 + h, sm + HBIAS[h]);
 #endif
-      const uint32_t db = 0x10000u + (uint32_t)(ai * 2 + which) * 64u;
-      bg = gamma_mt_d0(bc, gd0, key, (long)(row0 + r), step_id, db);
+      bg = gamma_mt_d0(bc, gd0, key, (long)(row0 + r), step_id, bi.db);
     }
     {
       const float pc = dpp_f<kDppQuadXor1>(bc), pg = dpp_f<kDppQuadXor1>(bg);  // every lane of the wave
@@ -1253,7 +1114,7 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
         const int ra = bitem >> 1, r = ra / A, ai = ra - r * A, e = row0 + r;
         const float al = bc, be = pc;
         const float s01 = beta_sample01(bg, pg);
-        const float act = (s01 - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
+        const float act = beta_action(s01, lo, hi);
         ACT[r * 24 + ai] = act;
         if (e < E) {
           a.s_actions[((long)t * E + e) * A + ai] = act;
@@ -1268,79 +1129,13 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
     ROLL_STAMP(t, 3);
     // ---- env step (k_rollout's: 32 lanes per env) ----
     if (tid < 32 * R) {
-#pragma clang fp contract(off)
       const int r = tid >> 5, i0 = tid & 31, e = row0 + r;
-      const bool live = e < E;
-      const bool reset = EVI[EV_AR * R + r] != 0;
-      float* q = Q + r * LDQ;
-      float* xo = XO + r * LDQ;
-      const float* ar = ACT + r * 24;
-      if (live && reset) {
-        const uint32_t rsd = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          if (i < O) {
-            uint32_t rr[4];
-            philox4x32(rc, (uint32_t)i, 0u, 0u, rsd, 0x5EED5EEDu, rr);
-            const float v = (0.1f * ((2.0f * u01(rr[0])) - 1.0f));
-            q[i] = v;
-            xo[i] = v;
-          }
-        }
-        if (i0 == 0) {
-          EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-          EVI[EV_T * R + r] = 0;
-          EV[EV_EPR * R + r] = 0.0f;
-          EVI[EV_EPL * R + r] = 0;
-          EV[EV_DONE * R + r] = 0.0f;
-          EVI[EV_AR * R + r] = 0;
-          a.s_rewards[(long)t * E + e] = 0.0f;
-        }
-      } else if (live) {
-        float qo[NCH], qn[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          qo[c] = i < O ? q[i] : 0.0f;
-          qn[c] = i < O ? q[i + 1 < O ? i + 1 : 0] : 0.0f;
-        }
-        float q0_new = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int i = 32 * c + i0;
-          if (i < O) {
-            const float ai = fminf(fmaxf(ar[i % A], a.lo), a.hi);
-            const float nq = __fmaf_rn(0.9f, qo[c], __fmaf_rn(0.1f, ai, (0.05f * qn[c])));
-            q[i] = nq;
-            xo[i] = nq;
-            if (c == 0) q0_new = nq;
-          }
-        }
-        if (i0 == 0) {
-          const float vel = ((q0_new - qo[0]) / 0.05f);
-          float ctrl = 0.0f;
-          for (int k = 0; k < A; ++k) {
-            const float ak = fminf(fmaxf(ar[k], a.lo), a.hi);
-            ctrl = (ctrl + ((0.1f * ak) * ak));
-          }
-          const float rw = (vel - ctrl);
-          const int tt = EVI[EV_T * R + r] + 1;
-          EVI[EV_T * R + r] = tt;
-          const bool tr = tt >= 1000;
-          a.s_rewards[(long)t * E + e] = rw;
-          EV[EV_DONE * R + r] = tr ? 1.0f : 0.0f;
-          const float epr = (EV[EV_EPR * R + r] + rw);
-          EV[EV_EPR * R + r] = epr;
-          const int epl = EVI[EV_EPL * R + r] + 1;
-          EVI[EV_EPL * R + r] = epl;
-          if (tr) {
-            EV[EV_FR * R + r] += epr;
-            EV[EV_FL * R + r] += (float)epl;
-            EV[EV_FC * R + r] += 1.0f;
-          }
-          EVI[EV_AR * R + r] = tr ? 1 : 0;
-        }
+      if (e < E) {
+        chee_lanes_step<R, NCH>(EV, r, i0, O, A, Q + r * LDQ, XO + r * LDQ, ACT + r * 24, a.lo, a.hi,
+                                [&](const EnvLaneOut& o) {
+                                  a.s_rewards[(long)t * E + e] = o.reward;
+                                  EV[EV_DONE * R + r] = o.fin ? 1.0f : 0.0f;
+                                });
       }
     }
     // the first Marsaglia-Tsang attempt's draws of the next step (independent of the network)
@@ -1349,26 +1144,7 @@ __global__ __launch_bounds__(kRVThreads) void k_rollout_v(RolloutArgs a) {
     ROLL_STAMP(t, 4);
   }
   // ---- epilogue: next_obs / next_done and the env state back to HBM ----
-  for (int idx = tid; idx < R * O; idx += kRVThreads) {
-    const int r = idx / O, ff = idx - r * O, e = row0 + r;
-    if (e < E) {
-      a.next_obs[(long)e * O + ff] = XO[r * LDQ + ff];
-      sv.q[(long)e * O + ff] = Q[r * LDQ + ff];
-    }
-  }
-  if (tid < R && row0 + tid < E) {
-    const int e = row0 + tid;
-    a.next_done[e] = EV[EV_DONE * R + tid];
-    sv.autoreset[e] = EVI[EV_AR * R + tid];
-    sv.t[e] = EVI[EV_T * R + tid];
-    sv.rseed[e] = (uint32_t)EVI[EV_RSEED * R + tid];
-    sv.rcount[e] = (uint32_t)EVI[EV_RCOUNT * R + tid];
-    sv.ep_ret[e] = EV[EV_EPR * R + tid];
-    sv.ep_len[e] = EVI[EV_EPL * R + tid];
-    sv.fin_ret[e] = EV[EV_FR * R + tid];
-    sv.fin_len[e] = EV[EV_FL * R + tid];
-    sv.fin_cnt[e] = EV[EV_FC * R + tid];
-  }
+  env_slots_store<R, kRVThreads>(EV, XO, Q, LDQ, sv, a.next_obs, a.next_done, row0, E, O, tid);
 }
 
 // =============================================================================================

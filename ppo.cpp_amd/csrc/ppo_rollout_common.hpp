@@ -1,8 +1,11 @@
 // ppo_rollout_common.hpp — building blocks of the persistent kernels of the 256-wide LayerNorm-Beta
 // agent: k_rollout / k_values (ppo_rollout.hip) and k_eval (ppo_eval.hip). LDS geometry, the per-env
-// scalar slots and the env step on them (env_lane_step, also k_rollout4's), the staged small
-// parameters, the register-resident weight slices and one trunk forward for the rows in XS. Kernels that use them in the same order produce bitwise identical
-// results (and bitwise k_act3's, whose blocks of ppo_act_common.hpp they are built from).
+// scalar slots, their load / store (env_slots_load / env_slots_store), the episode contract on them
+// (ev_autoreset, ev_step_account) and the env step on them (env_lane_step for a kind with a DevEnv,
+// chee_lanes_step for the cheetah; k_rollout_v uses them too, k_rollout4 env_lane_step), the staged small
+// parameters, the register-resident weight slices and one trunk forward for the rows in XS. Kernels
+// that use them in the same order produce bitwise identical results (and bitwise k_act3's, whose
+// blocks of ppo_act_common.hpp they are built from).
 //
 // A translation unit of the diagnostic stamps build defines ROLL_STAMP / RDBG / kRdbgEnv before it
 // includes this file; without them the hooks compile to nothing.
@@ -58,22 +61,107 @@ struct RollGeo {
 enum { EV_DONE = 0, EV_AR, EV_T, EV_RSEED, EV_RCOUNT, EV_EPR, EV_EPL, EV_FR, EV_FL, EV_FC,
        EV_WOC, EV_WRA, EV_WRM, EV_WRV, EV_WRC, EV_NSLOT };
 
-// One env step of a kind with a DevEnv, by lane 0 of the env's lane group in a persistent kernel: the
-// autoreset or the step, and the episode contract on the env's EV slots (R envs per workgroup, env r).
-//   * an env whose episode finished resets on the next step: reward 0, not finished, a new episode
-//     from reset number EV_RCOUNT of its Philox stream, the episode counters cleared
-//   * otherwise the step from the env's clipped actions; fin = terminated or truncated (EV_T reached
-//     MAX_STEPS); the step joins the running episode (EV_EPR, EV_EPL), a finished episode the totals
-//     (EV_FR, EV_FL, EV_FC), and EV_AR carries fin to the next step
-// Leaves the state in q and the raw observation in xo (the env's LDS rows). The caller does its own
-// part with the outcome: the rollout's reward and EV_DONE stores, the wrapper chain (term, not fin,
-// goes to NormalizeReward), the evaluation's episode event.
+// The ten per-env scalars and the q / obs rows of a workgroup's R envs [row0, row0 + R) between global
+// memory and LDS, by all NT threads: the prologue and the epilogue of a persistent kernel. obs is the
+// agent's next input ([E][O]); next_done may be null (the evaluation has none: EV_DONE is not used).
+// A row past the last env E - 1 loads zero rows and env E - 1's scalars, and is not stored. The
+// caller's barrier follows the load. (k_rollout4 keeps its own passes, which also move the wrapper
+// chain's rows and slots: DESIGN 5u.)
+template <int R, int NT>
+PPO_DEV void env_slots_load(float* EV, float* XO, float* Q, int ldq, const SynthArgs& sv, const float* obs,
+                            const float* next_done, int row0, int E, int O, int tid) {
+  int* EVI = reinterpret_cast<int*>(EV);
+  for (int idx = tid; idx < R * O; idx += NT) {
+    const int r = idx / O, f = idx - r * O, e = row0 + r;
+    XO[r * ldq + f] = e < E ? obs[(long)e * O + f] : 0.0f;
+    Q[r * ldq + f] = e < E ? sv.q[(long)e * O + f] : 0.0f;
+  }
+  if (tid < R) {
+    const int e = min(row0 + tid, E - 1);
+    if (next_done) EV[EV_DONE * R + tid] = next_done[e];
+    EVI[EV_AR * R + tid] = sv.autoreset[e];
+    EVI[EV_T * R + tid] = sv.t[e];
+    EVI[EV_RSEED * R + tid] = (int)sv.rseed[e];
+    EVI[EV_RCOUNT * R + tid] = (int)sv.rcount[e];
+    EV[EV_EPR * R + tid] = sv.ep_ret[e];
+    EVI[EV_EPL * R + tid] = sv.ep_len[e];
+    EV[EV_FR * R + tid] = sv.fin_ret[e];
+    EV[EV_FL * R + tid] = sv.fin_len[e];
+    EV[EV_FC * R + tid] = sv.fin_cnt[e];
+  }
+}
+template <int R, int NT>
+PPO_DEV void env_slots_store(const float* EV, const float* XO, const float* Q, int ldq, const SynthArgs& sv, float* obs,
+                             float* next_done, int row0, int E, int O, int tid) {
+  const int* EVI = reinterpret_cast<const int*>(EV);
+  for (int idx = tid; idx < R * O; idx += NT) {
+    const int r = idx / O, f = idx - r * O, e = row0 + r;
+    if (e < E) {
+      obs[(long)e * O + f] = XO[r * ldq + f];
+      sv.q[(long)e * O + f] = Q[r * ldq + f];
+    }
+  }
+  if (tid < R && row0 + tid < E) {
+    const int e = row0 + tid;
+    if (next_done) next_done[e] = EV[EV_DONE * R + tid];
+    sv.autoreset[e] = EVI[EV_AR * R + tid];
+    sv.t[e] = EVI[EV_T * R + tid];
+    sv.rseed[e] = (uint32_t)EVI[EV_RSEED * R + tid];
+    sv.rcount[e] = (uint32_t)EVI[EV_RCOUNT * R + tid];
+    sv.ep_ret[e] = EV[EV_EPR * R + tid];
+    sv.ep_len[e] = EVI[EV_EPL * R + tid];
+    sv.fin_ret[e] = EV[EV_FR * R + tid];
+    sv.fin_len[e] = EV[EV_FL * R + tid];
+    sv.fin_cnt[e] = EV[EV_FC * R + tid];
+  }
+}
+
+// The episode contract on env r's EV slots (R envs per workgroup), by one lane of the env's group:
+//   * an env whose episode finished (EV_AR) resets on the next step: reward 0, not finished, a new
+//     episode from reset number EV_RCOUNT of its Philox stream, the episode counters cleared
+//     (ev_autoreset, after the draws of reset number rc)
+//   * otherwise the step; fin = terminated or truncated (EV_T reached max_steps); the step joins the
+//     running episode (EV_EPR, EV_EPL), a finished episode the totals (EV_FR, EV_FL, EV_FC), and EV_AR
+//     carries fin to the next step (ev_step_account, from the step's reward and termination flag)
+// The caller does its own part with the outcome: the rollout's reward and EV_DONE stores, the wrapper
+// chain (term, not fin, goes to NormalizeReward), the evaluation's episode event.
 struct EnvLaneOut {
   float reward, term;  // term: 1.0f when the step terminated the episode (never on truncation)
   bool fin, reset;
   float epr;           // the episode's return and length up to this step (set when !reset)
   int epl;
 };
+template <int R>
+PPO_DEV void ev_autoreset(float* EV, int r, uint32_t rc) {
+  int* EVI = reinterpret_cast<int*>(EV);
+  EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
+  EVI[EV_T * R + r] = 0;
+  EV[EV_EPR * R + r] = 0.0f;
+  EVI[EV_EPL * R + r] = 0;
+  EVI[EV_AR * R + r] = 0;
+}
+template <int R>
+PPO_DEV void ev_step_account(float* EV, int r, int max_steps, EnvLaneOut& out) {
+#pragma clang fp contract(off)
+  int* EVI = reinterpret_cast<int*>(EV);
+  const int tt = EVI[EV_T * R + r] + 1;
+  EVI[EV_T * R + r] = tt;
+  out.fin = (out.term != 0.0f) || tt >= max_steps;  // done = terminated or truncated
+  out.epr = (EV[EV_EPR * R + r] + out.reward);
+  EV[EV_EPR * R + r] = out.epr;
+  out.epl = EVI[EV_EPL * R + r] + 1;
+  EVI[EV_EPL * R + r] = out.epl;
+  if (out.fin) {
+    EV[EV_FR * R + r] += out.epr;
+    EV[EV_FL * R + r] += (float)out.epl;
+    EV[EV_FC * R + r] += 1.0f;
+  }
+  EVI[EV_AR * R + r] = out.fin ? 1 : 0;
+}
+
+// One env step of a kind with a DevEnv, by lane 0 of the env's lane group in a persistent kernel: the
+// autoreset or the step from the env's clipped actions, and the episode contract. Leaves the state in
+// q and the raw observation in xo (the env's LDS rows).
 template <int KIND, int R>
 PPO_DEV EnvLaneOut env_lane_step(float* EV, int r, float* q, float* xo, const float* act_row, float lo, float hi) {
 #pragma clang fp contract(off)
@@ -86,11 +174,7 @@ PPO_DEV EnvLaneOut env_lane_step(float* EV, int r, float* q, float* xo, const fl
   if (out.reset) {
     const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
     D::reset(rc, rs, s, o);
-    EVI[EV_RCOUNT * R + r] = (int)(rc + 1);
-    EVI[EV_T * R + r] = 0;
-    EV[EV_EPR * R + r] = 0.0f;
-    EVI[EV_EPL * R + r] = 0;
-    EVI[EV_AR * R + r] = 0;
+    ev_autoreset<R>(EV, r, rc);
   } else {
     if constexpr (!D::IN_PLACE) {
 #pragma unroll
@@ -100,19 +184,7 @@ PPO_DEV EnvLaneOut env_lane_step(float* EV, int r, float* q, float* xo, const fl
 #pragma unroll
     for (int k = 0; k < D::A; ++k) ac[k] = fminf(fmaxf(act_row[k], lo), hi);
     out.reward = D::step(s, ac, o, &out.term);
-    const int tt = EVI[EV_T * R + r] + 1;
-    EVI[EV_T * R + r] = tt;
-    out.fin = (out.term != 0.0f) || tt >= D::MAX_STEPS;  // done = terminated or truncated
-    out.epr = (EV[EV_EPR * R + r] + out.reward);
-    EV[EV_EPR * R + r] = out.epr;
-    out.epl = EVI[EV_EPL * R + r] + 1;
-    EVI[EV_EPL * R + r] = out.epl;
-    if (out.fin) {
-      EV[EV_FR * R + r] += out.epr;
-      EV[EV_FL * R + r] += (float)out.epl;
-      EV[EV_FC * R + r] += 1.0f;
-    }
-    EVI[EV_AR * R + r] = out.fin ? 1 : 0;
+    ev_step_account<R>(EV, r, D::MAX_STEPS, out);
   }
   if constexpr (!D::IN_PLACE) {
 #pragma unroll
@@ -121,6 +193,71 @@ PPO_DEV EnvLaneOut env_lane_step(float* EV, int r, float* q, float* xo, const fl
     for (int i = 0; i < D::O; ++i) xo[i] = o[i];
   }
   return out;
+}
+
+// The synthetic cheetah's step of env r, spread over the env's 32 lanes (lane i0 takes the elements
+// i0, i0 + 32, ... of the O <= 32 NCH) on the env's LDS rows, called by all 32 lanes of a live env:
+// the autoreset draw or the step (k_synth_step / k_synth_step_wide arithmetic: every old q is in
+// registers before any write), and on lane 0 the reward, the episode contract and then lane0(outcome),
+// the caller's own part, inside the branch taken (a reset's outcome is constants there).
+template <int R, int NCH, typename F>
+PPO_DEV void chee_lanes_step(float* EV, int r, int i0, int O, int A, float* q, float* xo, const float* ar, float lo,
+                             float hi, F&& lane0) {
+  int* EVI = reinterpret_cast<int*>(EV);
+  EnvLaneOut out{0.0f, 0.0f, false, EVI[EV_AR * R + r] != 0, 0.0f, 0};
+  if (out.reset) {
+    const uint32_t rs = (uint32_t)EVI[EV_RSEED * R + r], rc = (uint32_t)EVI[EV_RCOUNT * R + r];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int i = 32 * c + i0;
+      if (i < O) {
+        const float v = chee_reset_elem(rc, rs, i);
+        q[i] = v;
+        xo[i] = v;
+      }
+    }
+    if (i0 == 0) {
+      ev_autoreset<R>(EV, r, rc);
+      lane0(out);
+    }
+  } else {
+    float qo[NCH], qn[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int i = 32 * c + i0;
+      qo[c] = i < O ? q[i] : 0.0f;
+      qn[c] = i < O ? q[i + 1 < O ? i + 1 : 0] : 0.0f;
+    }
+    float q0_new = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int i = 32 * c + i0;
+      if (i < O) {
+        const float nq = chee_next_q(qo[c], chee_clip(ar[i % A], lo, hi), qn[c]);
+        q[i] = nq;
+        xo[i] = nq;
+        if (c == 0) q0_new = nq;
+      }
+    }
+    if (i0 == 0) {
+      out.reward = chee_reward_clip(q0_new, qo[0], ar, A, lo, hi);
+      ev_step_account<R>(EV, r, CHEE_MAX_STEPS, out);
+      lane0(out);
+    }
+  }
+}
+
+// Env r's step in a persistent kernel whose envs have 32 lanes each (k_rollout, k_eval), called by all
+// 32 lanes of a live env: the cheetah spreads its step over them, a kind with a DevEnv steps on lane 0
+// from its actions ar[0..A-1]. The outcome is lane 0's.
+template <int KIND, int R, int NCH, typename F>
+PPO_DEV void env_lanes_step(float* EV, int r, int i0, int O, int A, float* q, float* xo, const float* ar, float lo,
+                            float hi, F&& lane0) {
+  if constexpr (KIND == PSYN_CHEETAH) {
+    chee_lanes_step<R, NCH>(EV, r, i0, O, A, q, xo, ar, lo, hi, lane0);
+  } else {
+    if (i0 == 0) lane0(env_lane_step<KIND, R>(EV, r, q, xo, ar, lo, hi));
+  }
 }
 
 // staged small parameters of one trunk into LDS (biases, LayerNorm affine, head rows, head biases)

@@ -1,8 +1,10 @@
 // gymcpp/synthetic_cheetah.h — deterministic HalfCheetah-shaped env (O=17, A=6, actions in [-1,1],
-// 1000-step truncation, never terminates). Stands in for libs/gymcpp/mujoco/half_cheetah_v5.h
-// where libmujoco is unavailable. Bit-identical to the device env (include/ppo_synth_env.h) and to
-// the oracle (oracle/ppo_oracle.c): fp32, explicit fmaf, no contraction (compile with
-// -ffp-contract=off), Philox4x32-10 reset noise keyed (seed, 0x5EED5EED), counter (resets, i).
+// truncation after CHEE_MAX_STEPS steps, never terminates). Stands in for
+// libs/gymcpp/mujoco/half_cheetah_v5.h where libmujoco is unavailable. The arithmetic is
+// include/ppo_cheetah.h's, shared with the device env (include/ppo_synth_env.h), so the two are
+// bit-identical, and so is the oracle's own restatement (oracle/ppo_oracle.c): fp32, explicit fmaf, no
+// contraction (compile with -ffp-contract=off), Philox4x32-10 reset noise keyed
+// (seed, CHEE_RESET_KEY), counter (resets, i). step() is handed clipped actions.
 #pragma once
 
 #include <chrono>
@@ -10,6 +12,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/ppo_cheetah.h"
 #include "gym.h"
 
 namespace gymcpp {
@@ -27,7 +30,7 @@ inline void philox4x32_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, 
 }
 
 class SyntheticCheetah final : public Environment {
-  static constexpr int kO = 17, kA = 6, kMaxSteps = 1000;
+  static constexpr int kO = 17, kA = 6, kMaxSteps = CHEE_MAX_STEPS;
   std::vector<float> q_ = std::vector<float>(kO, 0.0f), nq_ = std::vector<float>(kO, 0.0f);
   uint32_t rseed_ = 1, rcount_ = 0;
   int elapsed_ = kMaxSteps + 1;
@@ -43,9 +46,9 @@ class SyntheticCheetah final : public Environment {
     if (seed > 0) { rseed_ = (uint32_t)seed; rcount_ = 0; }
     for (int i = 0; i < kO; ++i) {
       uint32_t r[4];
-      philox4x32_host(rcount_, (uint32_t)i, 0u, 0u, rseed_, 0x5EED5EEDu, r);
+      philox4x32_host(rcount_, (uint32_t)i, 0u, 0u, rseed_, CHEE_RESET_KEY, r);
       const float u = ((float)(r[0] >> 8) + 0.5f) * 5.9604644775390625e-8f;
-      q_[i] = 0.1f * (2.0f * u - 1.0f);
+      q_[i] = chee_reset_value(u);
     }
     rcount_ += 1;
     elapsed_ = 0;
@@ -58,12 +61,9 @@ class SyntheticCheetah final : public Environment {
       }
     }
     const float xb = q_[0];
-    for (int i = 0; i < kO; ++i) nq_[i] = std::fma(0.9f, q_[i], std::fma(0.1f, a[i % kA], 0.05f * q_[(i + 1) % kO]));
+    for (int i = 0; i < kO; ++i) nq_[i] = chee_next_q(q_[i], a[i % kA], q_[(i + 1) % kO]);
     q_.swap(nq_);
-    const float vel = (q_[0] - xb) / 0.05f;
-    float ctrl = 0.0f;
-    for (int k = 0; k < kA; ++k) ctrl = ctrl + 0.1f * a[k] * a[k];
-    const float reward = vel - ctrl;
+    const float reward = chee_reward(q_[0], xb, a, kA);
     ++elapsed_;
     return {ObsView{q_.data(), kO}, reward, false, elapsed_ >= kMaxSteps};
   }

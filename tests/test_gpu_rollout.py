@@ -33,13 +33,17 @@ def snapshot(tr):
 @pytest.mark.parametrize("agent,env_id,E,iters", [("ac", "HalfCheetah-v5", 200, 9), ("ac", "Hopper-v5", 37, 9),
                                                   ("ac", "HalfCheetah-v5", 998, 2), ("ac", "Ant-v5", 96, 3),
                                                   ("ppo", "HalfCheetah-v5", 37, 9),
-                                                  ("ppo", "Hopper-v5", 20, 2), ("ppo", "Humanoid-v4", 40, 2)])
+                                                  ("ppo", "Hopper-v5", 20, 2), ("ppo", "Humanoid-v4", 40, 2),
+                                                  ("ac", "Ant-v5", 17, 9), ("ppo", "Humanoid-v4", 20, 9)])
 def test_persistent_rollout_bitwise_equals_per_step(agent, env_id, E, iters):
     """AC agent: the persistent rollout (k_rollout_v, the VALU form with 2 envs per workgroup, at
     E <= 512 and O <= 32 — E = 200 / 37 here; k_rollout, 16 envs per workgroup on MFMA, at E = 998
     and for Ant's O = 105) + k_values vs k_act3 + k_synth_step. PPO agent: k_rollout4 + k_values4 vs
     k_act4 (act_kernel=4) + k_synth_step(_wide), with the PPO wrapper chain (ppo:41-49) fused into
-    both (Humanoid: O = 376, A = 17, two head tiles, actions clipped to [-0.4, 0.4])."""
+    both (Humanoid: O = 376, A = 17, two head tiles, actions clipped to [-0.4, 0.4]). The last two rows
+    run the autoreset branch of the persistent kernels at O > 32 (9 x 128 = 1 152 steps: every env is
+    truncated and reset inside a rollout): k_rollout with four 32-element chunks per env lane (Ant,
+    E = 17: one full 16-env block and a ragged one) and k_rollout4's multi-group element loop."""
     T = 128
     C = ppo_amd.ACPPOConfig if agent == "ac" else ppo_amd.PPOConfig
     cfg = C(env_id=env_id, num_envs=E, num_steps=T, num_minibatches=4, update_epochs=2, total_timesteps=E * T * iters)
