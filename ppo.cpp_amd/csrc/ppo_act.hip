@@ -14,7 +14,7 @@
 //  * heads are MFMAs (split-K over the waves' features, partials reduced through LDS);
 //  * Beta sampling runs one (row, action, alpha|beta) item per thread, so the two Marsaglia-Tsang
 //    gamma draws and their lgamma/digamma chains run side by side.
-// The per-(row, action) arithmetic and the Philox counters are the ones of k_act / k_act2, so
+// The per-(row, action) arithmetic and the Philox counters are the ones of k_act2 (ppo_dist.hpp), so
 // samples are identical for any batching.
 #include "ppo_act_common.hpp"
 
@@ -99,11 +99,7 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
     } else {
       if (tid < R * A) {
         const int r = tid / A, ai = tid - r * A;
-        uint32_t rr[4];
-        philox_draw(key, a.env_base + row0 + r, a.step_id, (uint32_t)(ai >> 1), rr);
-        float z0, z1;
-        box_muller(rr[0], rr[1], z0, z1);
-        nz0 = (ai & 1) ? z1 : z0;
+        nz0 = normal_z(key, a.env_base + row0 + r, a.step_id, ai);
       }
     }
   }
@@ -232,6 +228,8 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
   }
 #endif
   if constexpr (KIND == PPO_NET_LN_BETA) {
+    // This branch keeps its own text of the Beta head's terms: with the shared functions
+    // k_act3 has 6 to 7 more instructions and the per-step path measured over its speed bound.
     // stage 1: one (row, action, alpha|beta) item per thread
     for (int idx = tid; idx < R * A * 2; idx += kActThreads) {
       const BetaItem bi = beta_item(idx, A);
@@ -296,19 +294,10 @@ __global__ __launch_bounds__(512) void k_act3(ActArgs a) {
       } else if (a.mode == PPO_MEAN) {
         act = mu;
       } else {
-        float z = nz0;
-        if (idx != tid) {
-          uint32_t rr[4];
-          philox_draw(key, env, a.step_id, (uint32_t)(ai >> 1), rr);
-          float z0, z1;
-          box_muller(rr[0], rr[1], z0, z1);
-          z = (ai & 1) ? z1 : z0;
-        }
-        act = mu + z * sd;
+        act = mu + (idx == tid ? nz0 : normal_z(key, env, a.step_id, ai)) * sd;
       }
-      const float d = act - mu;
-      LPE[idx * 2 + 0] = -(d * d) / (2.0f * var) - lsd - kLz;
-      LPE[idx * 2 + 1] = kEntC + lsd;
+      LPE[idx * 2 + 0] = normal_logp_term(act, mu, var, lsd);
+      LPE[idx * 2 + 1] = normal_ent_term(lsd);
       if (valid) {
         if (a.action_out) a.action_out[(size_t)row * A + ai] = act;
         if (a.store_step >= 0) a.s_actions[((long)a.store_step * a.E + env) * A + ai] = act;

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "ppo_agent.hpp"
+#include "ppo_dist.hpp"
 #include "ppo_kernels.hpp"
 
 namespace act {
@@ -156,21 +157,6 @@ PPO_DEV int act_head_bias(const PackedLayout& K, int trunk, int h) {
   }
   return h < K.A ? K.ab3 + h : -1;
 }
-
-
-// The Beta head's per-block work items, shared by k_act3 and the persistent kernels: item idx of a
-// block's R x A x 2 is (row r, action ai, which: 0 alpha | 1 beta); its concentration comes from head
-// ai + which * A, and db is the base of its gamma sample's Philox draws.
-struct BetaItem {
-  int which, r, ai;
-  uint32_t db;
-};
-PPO_DEV BetaItem beta_item(int idx, int A) {
-  const int which = idx & 1, ra = idx >> 1, r = ra / A, ai = ra - r * A;
-  return BetaItem{which, r, ai, 0x10000u + (uint32_t)(ai * 2 + which) * 64u};
-}
-// the action on [lo, hi] from the Beta sample (or mean, or mode) on [0, 1]
-PPO_DEV float beta_action(float s01, float lo, float hi) { return (s01 - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo; }
 
 // act_layer with the A operands already in registers (weight-resident kernels): the same MFMA
 // chain in the same order as act_layer, so the results are bitwise equal.

@@ -13,6 +13,7 @@
 // per wave. Partial sums meet in LDS in a fixed order. Sampling uses the Philox contract of k_act2
 // (same counters), so samples match it for any batching.
 #include "ppo_agent.hpp"
+#include "ppo_dist.hpp"
 #include "ppo_kernels.hpp"
 
 namespace {
@@ -94,13 +95,7 @@ __global__ __launch_bounds__(256) void k_act4(ActArgs a) {
       i_b3[u] = P[K.ab3 + ia];
       i_lstd[u] = P[K.logstd + ia];
       if (a.mode == PPO_GIVEN) i_act[u] = a.action_in[(size_t)min(irow, a.n - 1) * A + ia];
-      if (a.mode == PPO_SAMPLE) {
-        uint32_t rr[4];
-        philox_draw(key, a.env_base + irow, a.step_id, (uint32_t)(ia >> 1), rr);
-        float z0, z1;
-        box_muller(rr[0], rr[1], z0, z1);
-        nz[u] = (ia & 1) ? z1 : z0;
-      }
+      if (a.mode == PPO_SAMPLE) nz[u] = normal_z(key, a.env_base + irow, a.step_id, ia);
     }
   }
   if (trunk == 0 && tid < R) {
@@ -200,9 +195,8 @@ __global__ __launch_bounds__(256) void k_act4(ActArgs a) {
       if (a.mode == PPO_GIVEN) act = valid ? i_act[u] : 0.0f;
       else if (a.mode == PPO_MEAN) act = mu;
       else act = mu + nz[u] * sd;
-      const float d = act - mu;
-      ITM[idx][0] = -(d * d) / (2.0f * var) - lsd - kLz;
-      ITM[idx][1] = kEntC + lsd;
+      ITM[idx][0] = normal_logp_term(act, mu, var, lsd);
+      ITM[idx][1] = normal_ent_term(lsd);
       if (valid) {
         if (a.action_out) a.action_out[(size_t)irow * A + ia] = act;
         if (a.store_step >= 0) a.s_actions[((long)a.store_step * a.E + env) * A + ia] = act;

@@ -25,33 +25,6 @@ PPO_DEV f4 pld4(PBuf b, int lane_floats, int uni_floats) {
   return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(b.r, lane_floats * 4, uni_floats * 4, 0));
 }
 
-// Z^T tile chain: out = W . in (+ bias), W row-major [NT_OUT*16][LDW].
-template <int NT_OUT, int NT_IN, int LDW, bool BIAS>
-PPO_DEV void mm_layer(f4 (&out)[NT_OUT], const f4 (&in)[NT_IN], const float* __restrict__ W,
-                      const float* __restrict__ bias, int lane) {
-  const int i = lane & 15, g = lane >> 4;
-  const PBuf wb = make_pbuf(W, NT_OUT * 16 * LDW);
-  const int lo = i * LDW + 4 * g;
-  if constexpr (BIAS) {
-    const PBuf bb = make_pbuf(bias, NT_OUT * 16);
-#pragma unroll
-    for (int ot = 0; ot < NT_OUT; ++ot) out[ot] = pld4(bb, 4 * g, 16 * ot);
-  } else {
-#pragma unroll
-    for (int ot = 0; ot < NT_OUT; ++ot) out[ot] = f4{0.f, 0.f, 0.f, 0.f};
-  }
-#pragma unroll
-  for (int t = 0; t < NT_IN; ++t) {
-    f4 w[NT_OUT];
-#pragma unroll
-    for (int ot = 0; ot < NT_OUT; ++ot) w[ot] = pld4(wb, lo, 16 * ot * LDW + 16 * t);
-#pragma unroll
-    for (int c = 0; c < 4; ++c)  // independent chains interleaved, each in its own order
-#pragma unroll
-      for (int ot = 0; ot < NT_OUT; ++ot) out[ot] = mfma16(w[ot][c], in[t][c], out[ot]);
-  }
-}
-
 // Workgroup barrier that orders LDS traffic only: waits for this wave's LDS ops (lgkmcnt) and
 // leaves global loads/stores in flight (a plain __syncthreads() may also drain vmcnt).
 PPO_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -192,38 +165,3 @@ PPO_DEV float head_dot(const f4 (&h)[NT], PBuf pb, int w, float b, int g) {
   }
   return row_allreduce(p) + b;
 }
-
-// Full trunk forward: returns the last hidden activation in h (width H). For the LN net, also
-// returns the layer-1/2 statistics (needed by the fused backward).
-template <int H, int KIND, int NTO>
-PPO_DEV void trunk_forward(const TrunkDev& T, const float* __restrict__ P, PBuf pb, const f4 (&xin)[NTO],
-                           f4 (&h)[H / 16], int lane) {
-  constexpr int NT = H / 16;
-  const int g = lane >> 4;
-  f4 a[NT];
-  mm_layer<NT, NTO, NTO * 16, true>(a, xin, P + T.W1, P + T.b1, lane);
-  if constexpr (KIND == PPO_NET_LN_BETA) {
-    float mu, rs;
-    ln_stats<NT>(a, mu, rs);
-    ln_normalize<NT>(a, mu, rs);
-    affine_relu<NT>(a, a, pb, T.g1, T.be1, g);
-  } else {
-    tanh_inplace<NT>(a);
-  }
-  mm_layer<NT, NT, H, true>(h, a, P + T.W2, P + T.b2, lane);
-  if constexpr (KIND == PPO_NET_LN_BETA) {
-    float mu, rs;
-    ln_stats<NT>(h, mu, rs);
-    ln_normalize<NT>(h, mu, rs);
-    affine_relu<NT>(h, h, pb, T.g2, T.be2, g);
-  } else {
-    tanh_inplace<NT>(h);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Per-row distribution math. Every g-lane of a row computes the same per-row values; action
-// dimensions are distributed over the 4 g-lanes (a = g, g+4, ...) and summed with row_allreduce.
-// ---------------------------------------------------------------------------------------------
-static constexpr float kLz = 0.91893853320467274178f;   // log(sqrt(2 pi))  (rl_utils.h:20)
-static constexpr float kEntC = 1.4189385332046727418f;  // 0.5 + 0.5 log(2 pi) (rl_utils.h:44)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ppo_carla_units.hpp"
+#include "ppo_dist.hpp"
 
 // ------------------------------------------------------------------------------------------
 // C-ABI
@@ -550,66 +551,34 @@ struct HeadBwdArgs {
   float* rowstat;  // [n][8]
 };
 
-PPO_DEV float softplus_grad(float x) {
-  if (x > 20.0f) return 1.0f;
-  const float e = expf(x);
-  return e / (e + 1.0f);
-}
-
 // loss -> d(dist_mu, dist_sigma pre-activations), d(value); the terms of the minibatch stats
 __global__ __launch_bounds__(64) void k_carla_head_bwd(HeadBwdArgs h) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= h.n) return;
-  const float invM = 1.0f / (float)h.n, c = h.clip;
-  const float logratio = h.lp[r] - h.old_logp[r];
-  const float ratio = expf(logratio);
-  float an = h.adv[r];
-  if (h.norm_adv) an = (an - h.advstat[0]) / (h.advstat[1] + 1e-8f);
-  const float rc = fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-  const float pg1 = -an * ratio, pg2 = -an * rc;
-  // d max(pg1, pg2) / d ratio; ties split the gradient (ATen maximum backward)
-  const float w1 = pg1 > pg2 ? 1.0f : (pg1 == pg2 ? 0.5f : 0.0f);
-  const float inr = (ratio >= 1.0f - c && ratio <= 1.0f + c) ? 1.0f : 0.0f;
-  const float dratio = w1 * (-an) + (1.0f - w1) * (-an) * inr;
-  const float g_logp = invM * dratio * ratio;
-  const float v = h.val[r], R = h.ret[r];
-  float g_v, vterm;
-  if (h.clip_vloss) {
-    const float vu = (v - R) * (v - R);
-    const float dv = v - h.old_v[r];
-    const float vcl = h.old_v[r] + fminf(fmaxf(dv, -c), c);
-    const float vc = (vcl - R) * (vcl - R);
-    vterm = fmaxf(vu, vc);
-    const float u1 = vu > vc ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-    const float in2 = (dv >= -c && dv <= c) ? 1.0f : 0.0f;
-    g_v = 0.5f * h.vf_coef * invM * (u1 * 2.0f * (v - R) + (1.0f - u1) * 2.0f * (vcl - R) * in2);
-  } else {
-    vterm = (v - R) * (v - R);
-    g_v = 0.5f * h.vf_coef * invM * 2.0f * (v - R);
-  }
-  const float g_ent = -h.ent_coef * invM;
+  const float invM = 1.0f / (float)h.n;
+  const float am = h.norm_adv ? h.advstat[0] : 0.f, as = h.norm_adv ? h.advstat[1] : 0.f;
+  const PpoSurrogate sl = ppo_surrogate(h.lp[r], h.old_logp[r], h.adv[r], h.norm_adv, am, as, h.clip, invM, h.ent_coef);
+  const PpoValueLoss vl = ppo_value_loss(h.val[r], h.ret[r], h.old_v[r], h.clip, h.clip_vloss, h.vf_coef, invM);
+  const float g_logp = sl.g_logp, g_ent = sl.g_ent;
   const float hi = h.P[h.hi], lo = h.P[h.lo];
   for (int ai = 0; ai < h.A; ++ai) {
     const float pm = h.hpre[(long)r * 2 * h.A + ai], ps = h.hpre[(long)r * 2 * h.A + h.A + ai];
-    const float al = softplusf_(pm) + h.beta_min, be = softplusf_(ps) + h.beta_min, ab = al + be;
-    float sv = (h.actions[(long)r * h.A + ai] - lo) / (hi - lo) * (1.0f - 0.0f) + 0.0f;
-    sv = fminf(fmaxf(sv, 0.0f + 1e-7f), 1.0f + 1e-7f);
-    const float psab = digammaf_(ab), tab = trigammaf_(ab);
-    const float dla = ((al - 1.0f) != 0.0f ? logf(sv) : 0.0f) + psab - digammaf_(al);
-    const float dlb = ((be - 1.0f) != 0.0f ? logf(1.0f - sv) : 0.0f) + psab - digammaf_(be);
-    const float dea = (ab - 2.0f) * tab - (al - 1.0f) * trigammaf_(al);
-    const float deb = (ab - 2.0f) * tab - (be - 1.0f) * trigammaf_(be);
-    h.dhead[(long)r * 2 * h.A + ai] = (g_logp * dla + g_ent * dea) * softplus_grad(pm);
-    h.dhead[(long)r * 2 * h.A + h.A + ai] = (g_logp * dlb + g_ent * deb) * softplus_grad(ps);
+    const float al = softplusf_(pm) + h.beta_min, be = softplusf_(ps) + h.beta_min;
+    const float sv = beta_unit_from_action(h.actions[(long)r * h.A + ai], lo, hi);
+    const float ab = al + be;
+    const BetaGrad bg = beta_grad(al, be, sv, digammaf_(al), digammaf_(be), digammaf_(ab), trigammaf_(al), trigammaf_(be),
+                                  trigammaf_(ab));
+    h.dhead[(long)r * 2 * h.A + ai] = (g_logp * bg.dla + g_ent * bg.dea) * softplus_d(pm);
+    h.dhead[(long)r * 2 * h.A + h.A + ai] = (g_logp * bg.dlb + g_ent * bg.deb) * softplus_d(ps);
   }
-  h.dval[r] = g_v;
+  h.dval[r] = vl.g_v;
   float* st = h.rowstat + (long)r * 8;
-  st[0] = fmaxf(pg1, pg2);
-  st[1] = vterm;
+  st[0] = sl.pg;
+  st[1] = vl.term;
   st[2] = h.ent[r];
-  st[3] = -logratio;
-  st[4] = (ratio - 1.0f) - logratio;
-  st[5] = fabsf(ratio - 1.0f) > c ? 1.0f : 0.0f;
+  st[3] = sl.okl;
+  st[4] = sl.kl;
+  st[5] = sl.clipfrac;
 }
 
 // row means of the stats, one block, fixed order: pg, 0.5*v, entropy, old_kl, kl, clipfrac

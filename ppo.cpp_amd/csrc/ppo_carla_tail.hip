@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ppo_carla_units.hpp"
+#include "ppo_dist.hpp"
 
 namespace {
 
@@ -22,6 +23,11 @@ __global__ void k_carla_pack(const float* __restrict__ vmeas, float* __restrict_
 // digamma) are computed by other threads in the fused tail's head (tail_head_rows) and reach the
 // combining expressions through LDS; the same barrier here keeps the two paths' fp contraction (a
 // producer's final multiply fused into its consumer's add) identical, so they agree bit for bit.
+// beta_unit (ppo_dist.hpp) switches on PPO_GIVEN / PPO_MEAN / PPO_ROACH; this file passes it PPO_CARLA_* modes
+static_assert((int)PPO_CARLA_SAMPLE == (int)PPO_SAMPLE && (int)PPO_CARLA_MEAN == (int)PPO_MEAN &&
+                  (int)PPO_CARLA_GIVEN == (int)PPO_GIVEN && (int)PPO_CARLA_ROACH == (int)PPO_ROACH,
+              "the CaRL sample types must be the MLP agents' values");
+
 PPO_DEV float opaque_(float x) {
   asm volatile("" : "+v"(x));
   return x;
@@ -47,32 +53,21 @@ PPO_DEV BetaConc beta_conc(const HeadArgs& h, float pre, SampleKey key, long env
 }
 // action ai of row r: the sample / mean / roach / given value and the action's log-prob and
 // entropy terms (carla_head_row adds them over actions in action order); writes action / alpha / beta
-PPO_DEV void beta_action(const HeadArgs& h, int r, int ai, const BetaConc& ca, const BetaConc& cb, float& lpt,
+PPO_DEV void carla_beta_terms(const HeadArgs& h, int r, int ai, const BetaConc& ca, const BetaConc& cb, float& lpt,
                          float& entt) {
   const float* P = h.P;
   const float hi = P[h.hi], lo = P[h.lo];
   const float al = ca.conc, be = cb.conc;
-  float sv;
-  if (h.mode == PPO_CARLA_GIVEN) {
-    sv = (h.action_in[(long)r * h.A + ai] - lo) / (hi - lo) * (1.0f - 0.0f) + 0.0f;
-    sv = fminf(fmaxf(sv, 0.0f + 1e-7f), 1.0f + 1e-7f);
-  } else if (h.mode == PPO_CARLA_MEAN) {
-    sv = al / (al + be);
-  } else if (h.mode == PPO_CARLA_ROACH) {
-    if (al > 1.0f && be > 1.0f) sv = (al - 1.0f) / (al + be - 2.0f);
-    else if (al <= 1.0f && be > 1.0f) sv = 0.0f;
-    else if (al > 1.0f && be <= 1.0f) sv = 1.0f;
-    else sv = al / (al + be);
-  } else {
-    sv = beta_sample01(ca.draw, cb.draw);
-  }
-  sv = opaque_(sv);
+  float given = 0.f;
+  if (h.mode == PPO_CARLA_GIVEN) given = beta_unit_from_action(h.action_in[(long)r * h.A + ai], lo, hi);
+  const float sv = opaque_(beta_unit(h.mode, al, be, ca.draw, cb.draw, given));
   const float ab = al + be;
   const float lgab = opaque_(lgammaf(ab)), dgab = opaque_(digammaf_(ab));
+  // the two terms keep their own text: the opaque_ barriers sit inside the expressions
   const float xa = opaque_(xlogyf_(al - 1.0f, sv)), xb = opaque_(xlogyf_(be - 1.0f, 1.0f - sv));
   lpt = opaque_(xa + xb + (lgab - (ca.lg + cb.lg)));
   entt = opaque_((ca.lg + cb.lg) - lgab - (2.0f - ab) * dgab - ((al - 1.0f) * ca.dg + (be - 1.0f) * cb.dg));
-  if (h.action) h.action[(long)r * h.A + ai] = (sv - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
+  if (h.action) h.action[(long)r * h.A + ai] = beta_action(sv, lo, hi);
   if (h.alpha) h.alpha[(long)r * h.A + ai] = al;
   if (h.beta) h.beta[(long)r * h.A + ai] = be;
 }
@@ -109,7 +104,7 @@ PPO_DEV void carla_head_row(const HeadArgs& h, int r, const float* pre, bool cop
     }
     const BetaConc ca = beta_conc(h, pm, key, env, ai, 0), cb = beta_conc(h, ps, key, env, ai, 1);
     float lpt, entt;
-    beta_action(h, r, ai, ca, cb, lpt, entt);
+    carla_beta_terms(h, r, ai, ca, cb, lpt, entt);
     lp += lpt;
     ent += entt;
   }
@@ -303,7 +298,7 @@ PPO_DEV void tail_head_rows(const HeadArgs& h, int r0, int rows, const float* pr
   {
     const int rl = tid / A, ai = tid - rl * A, r = r0 + rl;
     if (rl < rows && r < n)
-      beta_action(h, r, ai, cs[rl * 2 * A + ai], cs[rl * 2 * A + A + ai], terms[tid * 2], terms[tid * 2 + 1]);
+      carla_beta_terms(h, r, ai, cs[rl * 2 * A + ai], cs[rl * 2 * A + A + ai], terms[tid * 2], terms[tid * 2 + 1]);
   }
   __syncthreads();
   if (tid < rows && r0 + tid < n) {

@@ -205,28 +205,12 @@ PPO_DEV float trigammaf_(float x) {
   result += (1.0f + 1.0f / (2.0f * x) + ixx * (1.0f / 6.0f - ixx * (1.0f / 30.0f - ixx * (1.0f / 42.0f)))) / x;
   return result;
 }
-// digamma and trigamma of one argument x >= 1 in one pass (the Beta loss gradient needs both at
-// alpha, beta and alpha + beta): shift x to >= 6 with one v_rcp_f32 per step (at most 5, as
-// predicated selects), then the asymptotic series. ~2 ulp; ATen's calc_digamma / calc_trigamma
-// (IEEE divisions, shifts to 10 / by 6) agree to that accuracy.
-PPO_DEV void digamma_trigamma(float x, float& dg, float& tg) {
-  float d = 0.0f, t = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const bool m = x < 6.0f;
-    const float r = __builtin_amdgcn_rcpf(x);
-    d = m ? d - r : d;
-    t = m ? fmaf(r, r, t) : t;
-    x = m ? x + 1.0f : x;
-  }
-  const float r = __builtin_amdgcn_rcpf(x), r2 = r * r;
-  dg = d + logf(x) - 0.5f * r -
-       r2 * (1.0f / 12 - r2 * (1.0f / 120 - r2 * (1.0f / 252 - r2 * (1.0f / 240 - r2 * (1.0f / 132)))));
-  tg = t + r * (1.0f + 0.5f * r + r2 * (1.0f / 6 - r2 * (1.0f / 30 - r2 * (1.0f / 42 - r2 * (1.0f / 30)))));
-}
-// lgamma, digamma and trigamma of one argument x >= 1 from one shared shift: lgamma(x) =
-// Stirling(x + n) - log(x (x + 1) ... (x + n - 1)). Absolute lgamma error ~1e-6 near its zeros at
-// 1 and 2 (the shift's log cancels there), relative ~1e-7 elsewhere.
+// lgamma, digamma and trigamma of one argument x >= 1 from one shared shift (the Beta loss gradient
+// needs all three at alpha, beta and alpha + beta): shift x to >= 6 with one v_rcp_f32 per step (at
+// most 5, as predicated selects), then the asymptotic series; lgamma(x) = Stirling(x + n) -
+// log(x (x + 1) ... (x + n - 1)). Digamma / trigamma ~2 ulp (ATen's calc_digamma / calc_trigamma,
+// IEEE divisions and shifts to 10 / by 6, agree to that accuracy); absolute lgamma error ~1e-6 near
+// its zeros at 1 and 2 (the shift's log cancels there), relative ~1e-7 elsewhere.
 PPO_DEV void lgamma_digamma_trigamma(float x, float& lg, float& dg, float& tg) {
   float d = 0.0f, t = 0.0f, prod = 1.0f;
 #pragma unroll

@@ -90,6 +90,7 @@ __global__ __launch_bounds__(512) void k_eval(EvalArgs a) {
       const float* ia = ITM + (idx * 2 + 0) * 4;
       const float* ib = ITM + (idx * 2 + 1) * 4;
       const float al = ia[0], be = ib[0];
+      // own three-way switch (no PPO_GIVEN here; with beta_unit k_eval measured over its speed bound)
       float s01;
       if (a.mode == PPO_MEAN) s01 = al / (al + be);
       else if (a.mode == PPO_ROACH) s01 = beta_roach01(al, be);

@@ -1,7 +1,7 @@
 // ppo_kernels.hip — hand-written gfx950 kernels of the rollout -> GAE -> PPO-update hot path.
 //
-//   k_act        Agent::get_action_and_value / get_value + rollout stores (ppo:145-157, :387-400;
-//                ac:212-249, :649-660). One wave = 16 env rows x one trunk, MFMA 16x16x4 f32.
+//   k_act2       Agent::get_action_and_value / get_value + rollout stores (ppo:145-157, :387-400;
+//                ac:212-249, :649-660). One workgroup = 16 or 32 env rows x one trunk, MFMA 16x16x4 f32.
 //   k_fwdbwd     fused minibatch gather + forward + PPO loss + backward of one trunk
 //                (ppo:495-538, ac:815-875); emits H1/DZ1/DZ2/Xn for the dW GEMMs and the
 //                per-block "small gradient" slab (biases, LayerNorm affine, heads, logstd).
@@ -17,6 +17,7 @@
 //                CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0), per-step form (the fused
 //                form is env_lane_step in ppo_rollout.hip / ppo_eval.hip)
 #include "ppo_agent.hpp"
+#include "ppo_dist.hpp"
 #include "ppo_kernels.hpp"
 #include "ppo_wrap.hpp"
 #include "ppo_env_kinds.hpp"
@@ -29,120 +30,10 @@
 constexpr int kDwdAux = 0;
 
 // =============================================================================================
-// k_act
-// =============================================================================================
-template <int H, int KIND, int NTO>
-__global__ __launch_bounds__(64) void k_act(ActArgs a) {
-  constexpr int NT = H / 16;
-  const int lane = threadIdx.x, j = lane & 15, g = lane >> 4;
-  const int trunk = blockIdx.y;
-  const int row = blockIdx.x * 16 + j;
-  const bool valid = row < a.n;
-  const PackedLayout& K = a.K;
-  const float* __restrict__ P = a.P;
-  const float* xrow = valid ? a.x + (size_t)row * a.ldx : nullptr;
-  const long env = a.env_base + row;
-  const long srow = (long)a.store_step * a.E + env;  // storage row when storing
-
-  f4 xin[NTO];
-  load_input<NTO, KIND>(xin, xrow, K.O, P + (K.omean >= 0 ? K.omean : 0), P + (K.ostd >= 0 ? K.ostd : 0), g);
-  const PBuf pbuf = make_pbuf(P, K.size);
-  f4 h[NT];
-  trunk_forward<H, KIND, NTO>(K.tr[trunk], P, pbuf, xin, h, lane);
-
-  if (trunk == 0) {
-    const float v = head_dot<NT>(h, pbuf, K.cW3, P[K.cb3], g);
-    if (valid && g == 0) {
-      if (a.value_out) a.value_out[row] = v;
-      if (a.store_step >= 0) {
-        a.s_values[srow] = v;
-        a.s_dones[srow] = a.next_done ? a.next_done[row] : 0.0f;
-      }
-    }
-    if (valid && a.store_step >= 0)
-      for (int f = g; f < K.O; f += 4) a.s_obs[srow * K.O + f] = xrow[f];
-    return;
-  }
-  if (!a.need_actor) return;
-
-  const int A = K.A;
-  const SampleKey key = sample_key(a.seed, a.rank);
-  float lp = 0.0f, ent = 0.0f;
-  if constexpr (KIND == PPO_NET_TANH_NORMAL) {
-    for (int ai = 0; ai < A; ++ai) {
-      const float mu = head_dot<NT>(h, pbuf, K.aW3 + ai * H, P[K.ab3 + ai], g);
-      if ((ai & 3) == g) {
-        const float sd = expf(P[K.logstd + ai]);
-        const float var = sd * sd, lsd = logf(sd);
-        float act;
-        if (a.mode == PPO_GIVEN) {
-          act = valid ? a.action_in[(size_t)row * A + ai] : 0.0f;
-        } else if (a.mode == PPO_MEAN) {
-          act = mu;
-        } else {
-          uint32_t rr[4];
-          philox_draw(key, env, a.step_id, (uint32_t)(ai >> 1), rr);
-          float z0, z1;
-          box_muller(rr[0], rr[1], z0, z1);
-          act = mu + ((ai & 1) ? z1 : z0) * sd;
-        }
-        const float d = act - mu;
-        lp += -(d * d) / (2.0f * var) - lsd - kLz;
-        ent += kEntC + lsd;
-        if (valid) {
-          if (a.action_out) a.action_out[(size_t)row * A + ai] = act;
-          if (a.store_step >= 0) a.s_actions[srow * A + ai] = act;
-        }
-      }
-    }
-  } else {
-    const float hi = P[K.hi], lo = P[K.lo];
-    for (int ai = 0; ai < A; ++ai) {
-      const float pa = head_dot<NT>(h, pbuf, K.aW3 + ai * H, P[K.ab3 + ai], g);
-      const float pb = head_dot<NT>(h, pbuf, K.bW3 + ai * H, P[K.bb3 + ai], g);
-      if ((ai & 3) == g) {
-        const float al = softplusf_(pa) + 1.0f, be = softplusf_(pb) + 1.0f;
-        float s;
-        if (a.mode == PPO_GIVEN) {
-          const float av = valid ? a.action_in[(size_t)row * A + ai] : 0.5f * (hi + lo);
-          s = (av - lo) / (hi - lo) * (1.0f - 0.0f) + 0.0f;
-          s = fminf(fmaxf(s, 1e-7f), 1.0f + 1e-7f);
-        } else if (a.mode == PPO_MEAN) {
-          s = al / (al + be);
-        } else if (a.mode == PPO_ROACH) {
-          s = beta_roach01(al, be);
-        } else {
-          const float ga = gamma_mt(al, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 0) * 64u);
-          const float gb = gamma_mt(be, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 1) * 64u);
-          s = beta_sample01(ga, gb);
-        }
-        const float ab = al + be;
-        const float lga = lgammaf(al), lgb = lgammaf(be), lgab = lgammaf(ab);
-        lp += xlogyf_(al - 1.0f, s) + xlogyf_(be - 1.0f, 1.0f - s) + (lgab - (lga + lgb));
-        ent += (lga + lgb) - lgab - (2.0f - ab) * digammaf_(ab) -
-               ((al - 1.0f) * digammaf_(al) + (be - 1.0f) * digammaf_(be));
-        const float act = (s - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
-        if (valid) {
-          if (a.action_out) a.action_out[(size_t)row * A + ai] = act;
-          if (a.store_step >= 0) a.s_actions[srow * A + ai] = act;
-        }
-      }
-    }
-  }
-  lp = row_allreduce(lp);
-  ent = row_allreduce(ent);
-  if (valid && g == 0) {
-    if (a.logprob_out) a.logprob_out[row] = lp;
-    if (a.entropy_out) a.entropy_out[row] = ent;
-    if (a.store_step >= 0) a.s_logp[srow] = lp;
-  }
-}
-
-// =============================================================================================
-// k_act2 — the same agent forward as k_act, block-cooperative: a 256-thread workgroup owns
+// k_act2 — the agent forward, block-cooperative: a 256-thread workgroup owns
 // ROWS = 16*RG env rows of one trunk and its 4 waves SPLIT THE OUTPUT FEATURES (wave w computes
 // feature tiles [w*NT/4, (w+1)*NT/4) of every layer), so a rollout step of 4096 envs runs on
-// 2 x 4096/ROWS workgroups with 4x less serial MFMA work per wave than k_act. Activations are
+// 2 x 4096/ROWS workgroups with a quarter of a one-wave-per-16-rows forward's serial MFMA work per wave. Activations are
 // exchanged through LDS (one [ROWS][H] buffer); LayerNorm row moments are reduced over the four
 // waves through LDS; head outputs are reduced per row; the per-(row, action-dim) distribution math
 // runs one item per thread. Every weight byte is read once per workgroup.
@@ -347,38 +238,29 @@ __global__ __launch_bounds__(256) void k_act2(ActArgs a) {
       } else if (a.mode == PPO_MEAN) {
         act = mu;
       } else {
-        uint32_t rr[4];
-        philox_draw(key, env, a.step_id, (uint32_t)(ai >> 1), rr);
-        float z0, z1;
-        box_muller(rr[0], rr[1], z0, z1);
-        act = mu + ((ai & 1) ? z1 : z0) * sd;
+        act = mu + normal_z(key, env, a.step_id, ai) * sd;
       }
-      const float d = act - mu;
-      lp = -(d * d) / (2.0f * var) - lsd - kLz;
-      ent = kEntC + lsd;
+      lp = normal_logp_term(act, mu, var, lsd);
+      ent = normal_ent_term(lsd);
     } else {
       const float hi = P[K.hi], lo = P[K.lo];
       const float al = softplusf_(head_out(r, ai)) + 1.0f, be = softplusf_(head_out(r, A + ai)) + 1.0f;
-      float sv;
+      float ga = 0.f, gb = 0.f, given = 0.f;
       if (a.mode == PPO_GIVEN) {
-        const float av = valid ? a.action_in[(size_t)row * A + ai] : 0.5f * (hi + lo);
-        sv = (av - lo) / (hi - lo) * (1.0f - 0.0f) + 0.0f;
-        sv = fminf(fmaxf(sv, 1e-7f), 1.0f + 1e-7f);
-      } else if (a.mode == PPO_MEAN) {
-        sv = al / (al + be);
-      } else if (a.mode == PPO_ROACH) {
-        sv = beta_roach01(al, be);
-      } else {
-        const float ga = gamma_mt(al, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 0) * 64u);
-        const float gb = gamma_mt(be, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 1) * 64u);
-        sv = beta_sample01(ga, gb);
+        given = beta_unit_from_action(valid ? a.action_in[(size_t)row * A + ai] : 0.5f * (hi + lo), lo, hi);
+      } else if (a.mode != PPO_MEAN && a.mode != PPO_ROACH) {  // every other mode samples, as beta_unit does
+        ga = gamma_mt(al, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 0) * 64u);
+        gb = gamma_mt(be, key, env, a.step_id, 0x10000u + (uint32_t)(ai * 2 + 1) * 64u);
       }
+      const float sv = beta_unit(a.mode, al, be, ga, gb, given);
+      // order matters: lgammaf x 3, then digammaf_ of ab, al, be, then the action, as the parent had them; another
+      // order fuses two products differently and moves the entropy by up to 64 ulp
       const float ab = al + be;
       const float lga = lgammaf(al), lgb = lgammaf(be), lgab = lgammaf(ab);
-      lp = xlogyf_(al - 1.0f, sv) + xlogyf_(be - 1.0f, 1.0f - sv) + (lgab - (lga + lgb));
-      ent = (lga + lgb) - lgab - (2.0f - ab) * digammaf_(ab) -
-            ((al - 1.0f) * digammaf_(al) + (be - 1.0f) * digammaf_(be));
-      act = (sv - 0.0f) / (1.0f - 0.0f) * (hi - lo) + lo;
+      lp = beta_logp_term(al, be, sv, lga, lgb, lgab);
+      const float psab = digammaf_(ab), psa = digammaf_(al), psb = digammaf_(be);
+      ent = beta_ent_term(al, be, lga, lgb, lgab, psa, psb, psab);
+      act = beta_action(sv, lo, hi);
     }
     itm[r][ai][0] = lp;
     itm[r][ai][1] = ent;
@@ -535,20 +417,9 @@ __global__ __launch_bounds__(256) void k_fwdbwd(UpdArgs a) {
     if (trunk == 0) {
       const float v = head_dot<NT>(h2, pbuf, K.cW3, P[K.cb3], g);
       const float rt = valid ? a.ret[b] : 0.f, ov = valid ? a.val[b] : 0.f;
-      float gv;
-      if (a.clip_vloss) {
-        const float vu = (v - rt) * (v - rt);
-        const float dv = v - ov;
-        const float vcl = ov + fminf(fmaxf(dv, -c), c);
-        const float vc = (vcl - rt) * (vcl - rt);
-        st_v = fmaxf(vu, vc);
-        const float w1 = vu > vc ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-        const float inr = (dv >= -c && dv <= c) ? 1.0f : 0.0f;
-        gv = 0.5f * a.vf_coef * a.inv_m * (w1 * 2.0f * (v - rt) + (1.0f - w1) * 2.0f * (vcl - rt) * inr);
-      } else {
-        st_v = (v - rt) * (v - rt);
-        gv = 0.5f * a.vf_coef * a.inv_m * 2.0f * (v - rt);
-      }
+      const PpoValueLoss vl = ppo_value_loss(v, rt, ov, c, a.clip_vloss, a.vf_coef, a.inv_m);
+      float gv = vl.g_v;
+      st_v = vl.term;
       if (!valid) { gv = 0.f; st_v = 0.f; }
       // head weight / bias grads and dh2
 #pragma unroll
@@ -569,9 +440,8 @@ __global__ __launch_bounds__(256) void k_fwdbwd(UpdArgs a) {
             const float sd = expf(P[K.logstd + ai]);
             const float var = sd * sd, lsd = logf(sd);
             const float act = valid ? a.actions[b * A + ai] : mu;
-            const float d = act - mu;
-            lp += -(d * d) / (2.0f * var) - lsd - kLz;
-            ent += kEntC + lsd;
+            lp += normal_logp_term(act, mu, var, lsd);
+            ent += normal_ent_term(lsd);
 #pragma unroll
             for (int k = 0; k < 5; ++k)
               if ((ai >> 2) == k) { own_x[k] = act; own_p[k] = mu; }
@@ -584,12 +454,11 @@ __global__ __launch_bounds__(256) void k_fwdbwd(UpdArgs a) {
           const float pb = head_dot<NT>(h2, pbuf, K.bW3 + ai * H, P[K.bb3 + ai], g);
           if ((ai & 3) == g) {
             const float al = softplusf_(pa) + 1.0f, be = softplusf_(pb) + 1.0f;
-            const float av = valid ? a.actions[b * A + ai] : 0.5f * (hi + lo);
-            float s = (av - lo) / (hi - lo) * (1.0f - 0.0f) + 0.0f;
-            s = fminf(fmaxf(s, 1e-7f), 1.0f + 1e-7f);
+            const float s = beta_unit_from_action(valid ? a.actions[b * A + ai] : 0.5f * (hi + lo), lo, hi);
             const float ab = al + be;
             const float lga = lgammaf(al), lgb = lgammaf(be), lgab = lgammaf(ab);
-            lp += xlogyf_(al - 1.0f, s) + xlogyf_(be - 1.0f, 1.0f - s) + (lgab - (lga + lgb));
+            lp += beta_logp_term(al, be, s, lga, lgb, lgab);
+            // own text and order: beta_ent_term here fuses a product differently in five instantiations
             ent += (lga + lgb) - lgab - (2.0f - ab) * digammaf_(ab) -
                    ((al - 1.0f) * digammaf_(al) + (be - 1.0f) * digammaf_(be));
 #pragma unroll
@@ -601,22 +470,10 @@ __global__ __launch_bounds__(256) void k_fwdbwd(UpdArgs a) {
       lp = row_allreduce(lp);
       ent = row_allreduce(ent);
       // ---- PPO clipped surrogate (per row) ----
-      const float oldlp = valid ? a.logp[b] : lp;
-      const float logratio = lp - oldlp;
-      const float ratio = expf(logratio);
-      st_okl = -logratio;
-      st_kl = (ratio - 1.0f) - logratio;
-      st_cf = fabsf(ratio - 1.0f) > c ? 1.0f : 0.0f;
-      st_ent = ent;
-      float an = valid ? a.adv[b] : 0.f;
-      if (a.norm_adv) an = (an - adv_mean) / (adv_std + 1e-8f);
-      const float rc = fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-      const float pg1 = -an * ratio, pg2 = -an * rc;
-      st_pg = fmaxf(pg1, pg2);
-      const float w1 = pg1 > pg2 ? 1.0f : (pg1 == pg2 ? 0.5f : 0.0f);
-      const float inr = (ratio >= 1.0f - c && ratio <= 1.0f + c) ? 1.0f : 0.0f;
-      float g_logp = a.inv_m * (w1 * (-an) + (1.0f - w1) * (-an) * inr) * ratio;
-      float g_ent = -a.ent_coef * a.inv_m;
+      const PpoSurrogate sl = ppo_surrogate(lp, valid ? a.logp[b] : lp, valid ? a.adv[b] : 0.f, a.norm_adv, adv_mean,
+                                            adv_std, c, a.inv_m, a.ent_coef);
+      float g_logp = sl.g_logp, g_ent = sl.g_ent;
+      st_pg = sl.pg; st_okl = sl.okl; st_kl = sl.kl; st_cf = sl.clipfrac; st_ent = ent;
       if (!valid) { g_logp = 0.f; g_ent = 0.f; st_pg = st_okl = st_kl = st_cf = st_ent = 0.f; }
 
       // ---- pass 2: per owned action dim gradients wrt head pre-activations ----
@@ -630,18 +487,16 @@ __global__ __launch_bounds__(256) void k_fwdbwd(UpdArgs a) {
             const float sd = expf(P[K.logstd + ai]);
             const float var = sd * sd;
             const float d = own_x[k] - own_p[k];
+            // not normal_grad: (g_logp * d) / var here, g_logp * (d / var) in k_upd / k_upd2
             own_ga[k] = g_logp * d / var;                                 // d loss / d mu
             own_gb[k] = g_logp * (d * d / var - 1.0f) + g_ent;            // d loss / d logstd
           } else {
             const float al = softplusf_(own_p[k]) + 1.0f, be = softplusf_(own_q[k]) + 1.0f;
-            const float ab = al + be, s = own_x[k];
-            const float psab = digammaf_(ab), tab = trigammaf_(ab);
-            const float dla = ((al - 1.0f) != 0.0f ? logf(s) : 0.0f) + psab - digammaf_(al);
-            const float dlb = ((be - 1.0f) != 0.0f ? logf(1.0f - s) : 0.0f) + psab - digammaf_(be);
-            const float dea = (ab - 2.0f) * tab - (al - 1.0f) * trigammaf_(al);
-            const float deb = (ab - 2.0f) * tab - (be - 1.0f) * trigammaf_(be);
-            own_ga[k] = (g_logp * dla + g_ent * dea) * softplus_d(own_p[k]);
-            own_gb[k] = (g_logp * dlb + g_ent * deb) * softplus_d(own_q[k]);
+            const float ab = al + be;
+            const BetaGrad bg = beta_grad(al, be, own_x[k], digammaf_(al), digammaf_(be), digammaf_(ab), trigammaf_(al),
+                                          trigammaf_(be), trigammaf_(ab));
+            own_ga[k] = (g_logp * bg.dla + g_ent * bg.dea) * softplus_d(own_p[k]);
+            own_gb[k] = (g_logp * bg.dlb + g_ent * bg.deb) * softplus_d(own_q[k]);
           }
         }
       }
@@ -2504,15 +2359,6 @@ int launch_act(const ActArgs& a, hipStream_t s) {
       dim3 grid((a.n + 31) / 32, a.need_actor ? 2 : 1);
       hipLaunchKernelGGL((k_act2<H, KIND, NTO, 2>), grid, dim3(256), 0, s, a);
     }
-    return 0;
-  });
-}
-
-int launch_act_wave(const ActArgs& a, hipStream_t s) {
-  dim3 grid((a.n + 15) / 16, a.need_actor ? 2 : 1);
-  return dispatch_net(a.K, [&](auto H_, auto KIND_, auto NTO_) {
-    hipLaunchKernelGGL((k_act<decltype(H_)::value, decltype(KIND_)::value, decltype(NTO_)::value>), grid, dim3(64), 0,
-                       s, a);
     return 0;
   });
 }

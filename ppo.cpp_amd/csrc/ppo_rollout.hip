@@ -160,8 +160,9 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
       it[0] = c;
       it[1] = gs;
       if (!defer) {
-        float tg_unused;
-        lgamma_digamma_trigamma(c, it[2], it[3], tg_unused);
+        const Sf3 fc = SfStirling::at(c);
+        it[2] = fc.lg;
+        it[3] = fc.dg;
       }
     }
     lds_barrier();
@@ -182,11 +183,7 @@ __global__ __launch_bounds__(512) void k_rollout(RolloutArgs a) {
           d[2] = s01;
         }
       } else {
-        const float ab = al + be;
-        float lgab, psab, tab_unused;
-        lgamma_digamma_trigamma(ab, lgab, psab, tab_unused);
-        const float lga = ia[2], lgb = ib[2];
-        LPE[idx * 2 + 0] = xlogyf_(al - 1.0f, s01) + xlogyf_(be - 1.0f, 1.0f - s01) + (lgab - (lga + lgb));
+        LPE[idx * 2 + 0] = beta_logp_term(al, be, s01, ia[2], ib[2], SfStirling::at(al + be).lg);
       }
     }
     lds_barrier();
@@ -229,12 +226,7 @@ __global__ __launch_bounds__(256) void k_beta_logp(const float* __restrict__ sb,
   for (int ai = 0; ai < A; ++ai) {
     const float* d = sb + (row * A + ai) * 3;
     const float al = d[0], be = d[1], s01 = d[2];
-    float lga, lgb, lgab, u0, u1;
-    lgamma_digamma_trigamma(al, lga, u0, u1);
-    lgamma_digamma_trigamma(be, lgb, u0, u1);
-    const float ab = al + be;
-    lgamma_digamma_trigamma(ab, lgab, u0, u1);
-    lp += xlogyf_(al - 1.0f, s01) + xlogyf_(be - 1.0f, 1.0f - s01) + (lgab - (lga + lgb));
+    lp += beta_logp_term(al, be, s01, SfStirling::at(al).lg, SfStirling::at(be).lg, SfStirling::at(al + be).lg);
   }
   logp[row] = lp;
 }
@@ -519,6 +511,7 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
 #pragma unroll
       for (int u = 0; u < NI; ++u) {
         const int idx = min(tid + kR4Threads * u, R * A - 1), ir = idx / A, ia = idx - ir * A;
+        // normal_z's text, kept: the call moves the scalar spills of k_rollout4<24, 2, 4, 0>
         uint32_t rr[4];
         philox_draw(key, (long)(row0 + ir), step_id, (uint32_t)(ia >> 1), rr);
         float z0, z1;
@@ -546,8 +539,7 @@ __global__ __launch_bounds__(256) void k_rollout4(RolloutArgs a) {
         const float mu = (((HP[0][ia][ir] + HP[1][ia][ir]) + HP[2][ia][ir]) + HP[3][ia][ir]) + i_b3[u];
         const float sd = i_sd[u], var = i_var[u], lsd = i_lsd[u];
         const float act = mu + nz[u] * sd;
-        const float d = act - mu;
-        ITM[idx][0] = -(d * d) / (2.0f * var) - lsd - kLz;
+        ITM[idx][0] = normal_logp_term(act, mu, var, lsd);
         ACT[ir * 32 + ia] = act;
         if (irow < E) a.s_actions[((long)t * E + irow) * A + ia] = act;
       }

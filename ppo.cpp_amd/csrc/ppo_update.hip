@@ -26,6 +26,7 @@
 // Everything is reduced in a fixed order: results are bitwise reproducible run to run.
 #include "ppo_agent.hpp"
 #include <cstdlib>
+#include "ppo_dist.hpp"
 #include "ppo_kernels.hpp"
 
 #ifdef PPO_STAMPS
@@ -486,6 +487,7 @@ PPO_DEV void upd_loss(const UpdArgs& a, int trunk, int tid, int m0, float c, flo
       const bool valid = m0 + tid < a.M;
       const float v = pre(tid, 0);
       const float rt_ = ROWS[tid * 8 + 1], ov = ROWS[tid * 8 + 2];
+      // ppo_value_loss's text, kept: the call moves k_upd's VGPR spills
       float gv, sv;
       if (a.clip_vloss) {
         const float vu = (v - rt_) * (v - rt_);
@@ -516,46 +518,30 @@ PPO_DEV void upd_loss(const UpdArgs& a, int trunk, int tid, int m0, float c, flo
     const float hi = P[K.hi], lo = P[K.lo];
     const float pa = pre(row, ac), pbv = pre(row, A + ac);
     const float al = softplusf_(pa) + 1.0f, be = softplusf_(pbv) + 1.0f;
-    const float av = valid ? ACTN[row * A + ac] : 0.5f * (hi + lo);
-    float s = (av - lo) / (hi - lo) * (1.0f - 0.0f) + 0.0f;
-    s = fminf(fmaxf(s, 1e-7f), 1.0f + 1e-7f);
-    const float ab = al + be;
-    float lga, lgb, lgab, psa, psb, psab, ta, tb, tab;
-    lgamma_digamma_trigamma(al, lga, psa, ta);
-    lgamma_digamma_trigamma(be, lgb, psb, tb);
-    lgamma_digamma_trigamma(ab, lgab, psab, tab);
-    const float lpi = xlogyf_(al - 1.0f, s) + xlogyf_(be - 1.0f, 1.0f - s) + (lgab - (lga + lgb));
-    const float eni = (lga + lgb) - lgab - (2.0f - ab) * psab - ((al - 1.0f) * psa + (be - 1.0f) * psb);
+    const float s = beta_unit_from_action(valid ? ACTN[row * A + ac] : 0.5f * (hi + lo), lo, hi);
+    const Sf3 fa = SfStirling::at(al), fb = SfStirling::at(be), fab = SfStirling::at(al + be);
+    const float lpi = beta_logp_term(al, be, s, fa.lg, fb.lg, fab.lg);
+    const float eni = beta_ent_term(al, be, fa.lg, fb.lg, fab.lg, fa.dg, fb.dg, fab.dg);
     const float lp = group8_sum(item ? lpi : 0.0f), ent = group8_sum(item ? eni : 0.0f);
-    const float oldlp = valid ? ROWS[row * 8 + 1] : lp;
-    const float logratio = lp - oldlp;
-    const float ratio = expf(logratio);
-    float an = valid ? ROWS[row * 8 + 2] : 0.f;
-    if (a.norm_adv) an = (an - adv_mean) / (adv_std + 1e-8f);
-    const float rc = fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-    const float pg1 = -an * ratio, pg2 = -an * rc;
-    const float w1 = pg1 > pg2 ? 1.0f : (pg1 == pg2 ? 0.5f : 0.0f);
-    const float inr = (ratio >= 1.0f - c && ratio <= 1.0f + c) ? 1.0f : 0.0f;
-    float g_logp = a.inv_m * (w1 * (-an) + (1.0f - w1) * (-an) * inr) * ratio;
-    float g_ent = -a.ent_coef * a.inv_m;
-    if (!valid) { g_logp = 0.f; g_ent = 0.f; }
+    const PpoSurrogate sl = ppo_surrogate(lp, valid ? ROWS[row * 8 + 1] : lp, valid ? ROWS[row * 8 + 2] : 0.f,
+                                          a.norm_adv, adv_mean, adv_std, c, a.inv_m, a.ent_coef);
+    const float g_logp = valid ? sl.g_logp : 0.f, g_ent = valid ? sl.g_ent : 0.f;
     if (ai == 0 && valid) {  // the row's statistics, once per row
-      st_a = fmaxf(pg1, pg2);
+      st_a = sl.pg;
       st_c = ent;
-      st_d = -logratio;
-      st_e = (ratio - 1.0f) - logratio;
-      st_f = fabsf(ratio - 1.0f) > c ? 1.0f : 0.0f;
+      st_d = sl.okl;
+      st_e = sl.kl;
+      st_f = sl.clipfrac;
     }
     if (item) {
-      const float dla = ((al - 1.0f) != 0.0f ? logf(s) : 0.0f) + psab - psa;         // d lp / d alpha
-      const float dea = (ab - 2.0f) * tab - (al - 1.0f) * ta;                         // d ent / d alpha
-      const float dlb = ((be - 1.0f) != 0.0f ? logf(1.0f - s) : 0.0f) + psab - psb;  // d lp / d beta
-      const float deb = (ab - 2.0f) * tab - (be - 1.0f) * tb;                         // d ent / d beta
-      GG[row * LDG + ai] = (g_logp * dla + g_ent * dea) * softplus_d(pa);
-      GG[row * LDG + A + ai] = (g_logp * dlb + g_ent * deb) * softplus_d(pbv);
+      const BetaGrad bg = beta_grad(al, be, s, fa.dg, fb.dg, fab.dg, fa.tg, fb.tg, fab.tg);
+      GG[row * LDG + ai] = (g_logp * bg.dla + g_ent * bg.dea) * softplus_d(pa);
+      GG[row * LDG + A + ai] = (g_logp * bg.dlb + g_ent * bg.deb) * softplus_d(pbv);
     }
   } else {
-    // pass 1: per (row, action) log-prob / entropy terms and derivative pieces
+    // pass 1: per (row, action) log-prob / entropy terms and derivative pieces. Both heads keep their own text of
+    // the terms (the branch above calls ppo_dist.hpp): with the calls k_upd / k_upd32 leave the parent's
+    // resource rows. This Beta branch (A > 8) is not reachable through the C-ABI.
     for (int idx = tid; idx < R * A; idx += 256) {
       const int row = idx / A, ai = idx - row * A;
       const bool valid = m0 + row < a.M;
@@ -601,22 +587,14 @@ PPO_DEV void upd_loss(const UpdArgs& a, int trunk, int tid, int m0, float c, flo
         lp += ITM[(tid * A + ai) * ITS + 0];
         ent += ITM[(tid * A + ai) * ITS + 1];
       }
-      const float oldlp = valid ? ROWS[tid * 8 + 1] : lp;
-      const float logratio = lp - oldlp;
-      const float ratio = expf(logratio);
-      float an = valid ? ROWS[tid * 8 + 2] : 0.f;
-      if (a.norm_adv) an = (an - adv_mean) / (adv_std + 1e-8f);
-      const float rc = fminf(fmaxf(ratio, 1.0f - c), 1.0f + c);
-      const float pg1 = -an * ratio, pg2 = -an * rc;
-      const float w1 = pg1 > pg2 ? 1.0f : (pg1 == pg2 ? 0.5f : 0.0f);
-      const float inr = (ratio >= 1.0f - c && ratio <= 1.0f + c) ? 1.0f : 0.0f;
-      float g_logp = a.inv_m * (w1 * (-an) + (1.0f - w1) * (-an) * inr) * ratio;
-      float g_ent = -a.ent_coef * a.inv_m;
-      st_a = fmaxf(pg1, pg2);
+      const PpoSurrogate sl = ppo_surrogate(lp, valid ? ROWS[tid * 8 + 1] : lp, valid ? ROWS[tid * 8 + 2] : 0.f,
+                                            a.norm_adv, adv_mean, adv_std, c, a.inv_m, a.ent_coef);
+      float g_logp = sl.g_logp, g_ent = sl.g_ent;
+      st_a = sl.pg;
       st_c = ent;
-      st_d = -logratio;
-      st_e = (ratio - 1.0f) - logratio;
-      st_f = fabsf(ratio - 1.0f) > c ? 1.0f : 0.0f;
+      st_d = sl.okl;
+      st_e = sl.kl;
+      st_f = sl.clipfrac;
       if (!valid) { g_logp = 0.f; g_ent = 0.f; st_a = st_c = st_d = st_e = st_f = 0.f; }
       ROWS[tid * 8 + 3] = g_logp;
       ROWS[tid * 8 + 4] = g_ent;

@@ -9,7 +9,7 @@ Copies reached: k_act3 with one and two input blocks, k_act2
 k_carla_head; k_rollout + k_beta_logp, k_rollout_v + k_beta_logp, the per-step ppo_rollout_act, k_eval;
 k_upd's 8-lane group (A = 3, 6, 8) as bx6 / fp32 16x16x4 / k_upd32 / its mixed form, k_fwdbwd at hidden 256
 and 64, k_carla_head_bwd. Not reached through the C-ABI: k_upd's LDS item path for A > 8 (below), k_rollout
-with log-probs in the loop (ppo_rollout_synth always defers them for this agent), k_act (no caller).
+with log-probs in the loop (ppo_rollout_synth always defers them for this agent).
 
 Behaviour the reference shares and the tests expect: log-prob -inf at action = hi with beta > 1 (s = 1,
 log 0), NaN at an action above hi (scale_action's upper clamp is 1 + 1e-7f = 1 + 2^-23, so 1 - s < 0), and at

@@ -2,10 +2,10 @@
 (oracle/ref_harness.cpp width_cases()), through the C-ABI:
 
   ac256   AC agent, 2x256 LayerNorm trunks + Beta heads (ac:150-249), HalfCheetah O=17 / A=6
-          -> k_act (API act), k_act3 (rollout act), k_upd<256, LN_BETA> + k_dwf (update)
+          -> k_act3 (API act and rollout act), k_upd<256, LN_BETA> + k_dwf (update)
   ant256  the same agent at Ant-v5 O=105 / A=8 (cfg4)
   hum376  PPO agent, 2x64 tanh + Normal (ppo:120-157), Humanoid-v4 O=376 / A=17 (cfg2)
-          -> k_act (API act), k_act4 (rollout act: K-split, wide input), k_upd2 + k_dw2 (update)
+          -> k_act4 (API act and rollout act: K-split, wide input), k_upd2 + k_dw2 (update)
   gae_long / gae_t{1,7,33}  k_gae at cfg2's T=2048 (E=1024) and at ragged T (32-step load chunks)
 
 Tolerances (fp32; MFMA f32 chains vs LibTorch's CPU GEMMs, the same bars as test_gpu_parity.py):
