@@ -49,6 +49,16 @@
  * dynamics clip the four actions to [-1, 1] themselves; the termination flag reaches the wrapper
  * chain as CartPole's does. Not covered for this kind: the VALU rollout kernel (rollout_kernel=valu
  * is refused).
+ *
+ * A sixth kind, PSYN_ACROBOT (psyn_create_env("AcrobotContinuous-v1")), is the first whose step is a
+ * multi-stage integrator: Gymnasium's Acrobot-v1 ("book" dynamics, one RK4 step of 0.2 s per env step)
+ * with the torque clip(a, -1, 1) from one continuous action (O = 6: cos / sin of both angles and both
+ * speeds; A = 1; reward -1 per step and 0 on the terminating step; termination when the tip is above
+ * the bar, -cos theta1 - cos(theta1 + theta2) > 1; truncation after 500 steps), with the arithmetic of
+ * include/ppo_acrobot.h — bit for bit the host env ppo.cpp_amd/gymcpp/acrobot.h. Its state q [E, 6]
+ * holds theta1, theta2, theta1dot, theta2dot and two unused slots. Termination here is success: a
+ * shorter episode is the better one, and the termination flag reaches the wrapper chain as
+ * CartPole's does. rollout_kernel=valu is refused for this kind as well.
  */
 #ifndef PPO_SYNTH_ENV_H
 #define PPO_SYNTH_ENV_H
@@ -61,11 +71,12 @@ typedef struct psyn_env psyn_t;
 
 int psyn_create(int num_envs, int obs_dim, int act_dim, psyn_t** out);
 /* The env kinds. psyn_create gives PSYN_CHEETAH at any (obs_dim, act_dim). */
-enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1, PSYN_CARTPOLE = 2, PSYN_REACHER = 3, PSYN_QUADROTOR = 4 };
+enum { PSYN_CHEETAH = 0, PSYN_PENDULUM = 1, PSYN_CARTPOLE = 2, PSYN_REACHER = 3, PSYN_QUADROTOR = 4, PSYN_ACROBOT = 5 };
 /* By env id: "Pendulum-v1" (PSYN_PENDULUM: O = 3, A = 1, action space [-2, 2]),
  * "CartPoleContinuous-v1" (PSYN_CARTPOLE: O = 4, A = 1, action space [-1, 1]),
  * "ReacherPlanar-v0" (PSYN_REACHER: O = 10, A = 2, action space [-1, 1]^2),
- * "QuadrotorHover-v0" (PSYN_QUADROTOR: O = 18, A = 4, action space [-1, 1]^4) or
+ * "QuadrotorHover-v0" (PSYN_QUADROTOR: O = 18, A = 4, action space [-1, 1]^4),
+ * "AcrobotContinuous-v1" (PSYN_ACROBOT: O = 6, A = 1, action space [-1, 1]) or
  * "SyntheticCheetah-v0" (the env of psyn_create(num_envs, 17, 6)). Any other id, a NULL argument or
  * num_envs <= 0 is refused (-1, ppo_last_error lists the ids) before any HIP call. */
 int psyn_create_env(const char* env_id, int num_envs, psyn_t** out);

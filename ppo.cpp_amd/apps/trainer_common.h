@@ -37,6 +37,7 @@
 #include "../gymcpp/cartpole.h"
 #include "../gymcpp/reacher.h"
 #include "../gymcpp/quadrotor.h"
+#include "../gymcpp/acrobot.h"
 #include "tensorboard_logger.h"
 #include "../gymcpp/wrappers.h"
 
@@ -359,7 +360,8 @@ struct EnvSpec {
 // own_kind ids have dynamics of their own on the device and are created by id (psyn_create_env:
 // Pendulum-v1, Gymnasium's pendulum.py; CartPoleContinuous-v1, Gymnasium's cartpole.py with a continuous
 // force; ReacherPlanar-v0, Reacher-v5's task definition over the textbook two-link arm, not MuJoCo's
-// Reacher; QuadrotorHover-v0, the project's own hover task over the textbook Newton-Euler quadrotor).
+// Reacher; QuadrotorHover-v0, the project's own hover task over the textbook Newton-Euler quadrotor;
+// AcrobotContinuous-v1, Gymnasium's acrobot.py with a continuous torque).
 // Every other id runs the synthetic dynamics of include/ppo_synth_env.h at the observation / action
 // widths and action bounds of the reference's MuJoCo env (libs/gymcpp/mujoco/half_cheetah_v5.h:31-34,
 // humanoid_v4.h:27-30, ant_v5.h:38-41, hopper_v5.h:35-38). make_host: the host env; null for the
@@ -387,6 +389,7 @@ inline const std::vector<EnvEntry>& env_entries() {
       {"CartPoleContinuous-v1", {CART_OBS_DIM, CART_ACT_DIM, -1.0f, 1.0f}, true, make_host_env<gymcpp::CartPoleContinuous>},
       {"ReacherPlanar-v0", {REACH_OBS_DIM, REACH_ACT_DIM, -1.0f, 1.0f}, true, make_host_env<gymcpp::ReacherPlanar>},
       {"QuadrotorHover-v0", {QUAD_OBS_DIM, QUAD_ACT_DIM, -1.0f, 1.0f}, true, make_host_env<gymcpp::QuadrotorHover>},
+      {"AcrobotContinuous-v1", {ACRO_OBS_DIM, ACRO_ACT_DIM, -1.0f, 1.0f}, true, make_host_env<gymcpp::AcrobotContinuous>},
   };
   return k;
 }

@@ -1697,7 +1697,7 @@ extern "C" int psyn_create_env(const char* env_id, int E, psyn_t** out) {
     if (id == r.env_id) row = &r;
   if (!row)
     return fail("psyn_create_env: unknown env_id " + id +
-                " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0");
+                " (Pendulum-v1, SyntheticCheetah-v0), CartPoleContinuous-v1, ReacherPlanar-v0, QuadrotorHover-v0, AcrobotContinuous-v1");
   if (int rc = psyn_create(E, row->O, row->A, out)) return rc;
   (*out)->a.kind = row->kind;
   (*out)->act_lo = row->act_lo;

@@ -4,9 +4,11 @@
 //   PSYN_REACHER    ReacherPlanar-v0       Reacher-v5's task over the textbook two-link arm (not MuJoCo's)
 //   PSYN_QUADROTOR  QuadrotorHover-v0      this project's hover task over the textbook Newton-Euler
 //                                          quadrotor; it terminates
+//   PSYN_ACROBOT    AcrobotContinuous-v1   Gymnasium's acrobot.py ("book", RK4) with a continuous torque;
+//                                          it terminates, on success
 // DevEnv<KIND> is a kind's shape, its reset from the env's Philox stream and its step: the shared
-// arithmetic of include/ppo_{pendulum,cartpole,reacher,quadrotor}.h compiled for the device, bit for
-// bit the host envs gymcpp/{pendulum,cartpole,reacher,quadrotor}.h (no contraction, no device-library
+// arithmetic of include/ppo_{pendulum,cartpole,reacher,quadrotor,acrobot}.h compiled for the device, bit for
+// bit the host envs gymcpp/{pendulum,cartpole,reacher,quadrotor,acrobot}.h (no contraction, no device-library
 // trigonometry, correctly rounded divisions and square roots). kEnvKinds is the same kinds for the
 // host, one row each, and dispatch_env_kind turns a run-time kind into the compile-time one.
 // Used by the per-step env kernels k_env_reset / k_env_step (ppo_kernels.hip), by env_lane_step
@@ -25,13 +27,14 @@
 #include "../../include/ppo_cartpole.h"
 #include "../../include/ppo_reacher.h"
 #include "../../include/ppo_quadrotor.h"
+#include "../../include/ppo_acrobot.h"
 
 #include <type_traits>
 
 // the uniforms of reset number rc of the env keyed rs: counter (rc, i, 0, 0) for draw i, every kind's
 // reset stream. All kinds share one second key word; the cheetah's header names it (CHEE_RESET_KEY)
 // because the cheetah is the kind whose host env takes it from a shared header, and the host envs of
-// the other kinds (gymcpp/{pendulum,cartpole,reacher,quadrotor}.h) spell the same value themselves.
+// the other kinds (gymcpp/{pendulum,cartpole,reacher,quadrotor,acrobot}.h) spell the same value themselves.
 constexpr uint32_t kEnvResetKey = CHEE_RESET_KEY;
 PPO_DEV float env_reset_draw(uint32_t rc, uint32_t rs, int i) {
   uint32_t r[4];
@@ -135,6 +138,19 @@ struct DevEnv<PSYN_QUADROTOR> {  // s = (p, v, quaternion, omega); draws: p, v, 
   PPO_DEV static float step(float* s, const float* act, float* obs, float* term) { return quad_step(s, act, obs, term); }
 };
 
+template <>
+struct DevEnv<PSYN_ACROBOT> {  // s = (theta1, theta2, theta1dot, theta2dot); draws: those four
+  static constexpr int O = ACRO_OBS_DIM, A = ACRO_ACT_DIM, S = ACRO_STATE_DIM, MAX_STEPS = ACRO_MAX_STEPS, NTO = 1, NHT = 1;
+  static constexpr bool TERMINATES = true, IN_PLACE = false;
+  PPO_DEV static void reset(uint32_t rc, uint32_t rs, float* s, float* obs) {
+    float u[ACRO_STATE_DIM];
+    env_reset_draws(rc, rs, u);
+    acro_reset(u, s);
+    (void)acro_obs(s, obs);
+  }
+  PPO_DEV static float step(float* s, const float* act, float* obs, float* term) { return acro_step(s, act[0], obs, term); }
+};
+
 // the tile shape at which k_rollout, k_rollout4 and k_eval may be instantiated for an env kind: the
 // cheetah at any shape, every other kind at its own
 template <int KIND, int NTO, int NHT>
@@ -164,6 +180,7 @@ constexpr EnvKindRow kEnvKinds[] = {
     env_kind_row<PSYN_CARTPOLE>("CartPoleContinuous-v1", "PSYN_CARTPOLE", -1.0f, 1.0f),
     env_kind_row<PSYN_REACHER>("ReacherPlanar-v0", "PSYN_REACHER", -1.0f, 1.0f),
     env_kind_row<PSYN_QUADROTOR>("QuadrotorHover-v0", "PSYN_QUADROTOR", -1.0f, 1.0f),
+    env_kind_row<PSYN_ACROBOT>("AcrobotContinuous-v1", "PSYN_ACROBOT", -1.0f, 1.0f),
 };
 // the row of a kind; null for PSYN_CHEETAH and for a number that is no kind
 inline const EnvKindRow* env_kind_row_of(int kind) {
@@ -181,6 +198,7 @@ static int dispatch_env_kind(int kind, F&& f) {
     case PSYN_CARTPOLE: return f(std::integral_constant<int, PSYN_CARTPOLE>{});
     case PSYN_REACHER: return f(std::integral_constant<int, PSYN_REACHER>{});
     case PSYN_QUADROTOR: return f(std::integral_constant<int, PSYN_QUADROTOR>{});
+    case PSYN_ACROBOT: return f(std::integral_constant<int, PSYN_ACROBOT>{});
   }
   return -1;
 }

@@ -552,12 +552,14 @@ ENV_DIMS = {  # obs / act dims and action bounds of the reference's MuJoCo envs
     "ReacherPlanar-v0": (10, 2, -1.0, 1.0),
     # the project's own hover task over the textbook Newton-Euler quadrotor: O = 18 (two input tiles), A = 4
     "QuadrotorHover-v0": (18, 4, -1.0, 1.0),
+    # Gymnasium's acrobot.py ("book", RK4) with a continuous torque: it terminates, on success
+    "AcrobotContinuous-v1": (6, 1, -1.0, 1.0),
 }
 # env ids whose device env is created by id (psyn_create_env: an env kind of its own); every other id
 # runs the synthetic cheetah dynamics at the id's shape (psyn_create)
 # (a set by use; tests/test_reacher_cpu.py reads its last entry, so new ids go before it)
-DEVICE_ENV_KINDS = ("Pendulum-v1", "CartPoleContinuous-v1", "QuadrotorHover-v0", "ReacherPlanar-v0")
-PSYN_CHEETAH, PSYN_PENDULUM, PSYN_CARTPOLE, PSYN_REACHER, PSYN_QUADROTOR = 0, 1, 2, 3, 4
+DEVICE_ENV_KINDS = ("Pendulum-v1", "CartPoleContinuous-v1", "QuadrotorHover-v0", "AcrobotContinuous-v1", "ReacherPlanar-v0")
+PSYN_CHEETAH, PSYN_PENDULUM, PSYN_CARTPOLE, PSYN_REACHER, PSYN_QUADROTOR, PSYN_ACROBOT = 0, 1, 2, 3, 4, 5
 
 
 @dataclass
@@ -1225,7 +1227,7 @@ class SynthEnv:
     """Device-resident vector env (include/ppo_synth_env.h): SynthEnv(E, obs_dim, act_dim) is the
     synthetic HalfCheetah-shaped env; SynthEnv(E, env_id="Pendulum-v1") the env of that id
     (psyn_create_env: "Pendulum-v1" | "CartPoleContinuous-v1" | "ReacherPlanar-v0" |
-    "QuadrotorHover-v0" | "SyntheticCheetah-v0")."""
+    "QuadrotorHover-v0" | "AcrobotContinuous-v1" | "SyntheticCheetah-v0")."""
 
     def __init__(self, num_envs, obs_dim=None, act_dim=None, env_id=None):
         h = C.c_void_p()
@@ -1426,7 +1428,7 @@ def init_params(layout: Layout, seed=1, env_id=None, obs_mean=None, obs_std=None
             lo, hi = ENV_DIMS[env_id][2], ENV_DIMS[env_id][3]
         P[L.hi] = hi
         P[L.lo] = lo
-        # (Pendulum-v1 has no table: ppo_obs_norm refuses it and the identity is used; so it is for
+        # (Pendulum-v1 and AcrobotContinuous-v1 have no table: ppo_obs_norm refuses them and the identity is used; so it is for
         # CartPoleContinuous-v1, ReacherPlanar-v0 and QuadrotorHover-v0, which ppo_obs_norm answers with n = 0)
         if obs_mean is None and env_id in ENV_DIMS and env_id not in DEVICE_ENV_KINDS and ENV_DIMS[env_id][0] == O:
             table = obs_norm(env_id)

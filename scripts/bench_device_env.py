@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """AC agent on one of the device envs (Pendulum-v1, CartPoleContinuous-v1, ReacherPlanar-v0,
-QuadrotorHover-v0, or the synthetic cheetah as HalfCheetah-v5) at E = 4096, T = 128 (the metric
+QuadrotorHover-v0, AcrobotContinuous-v1, or the synthetic cheetah as HalfCheetah-v5) at E = 4096, T = 128 (the metric
 config's shape): the persistent rollout (k_rollout<NTO, 1, KIND>, or k_rollout_v for the cheetah at
 E <= 512, + k_beta_logp + k_values) against the per-step path (rollout=per_step: k_act3 +
 k_env_step<KIND> or k_synth_step per step), alternating, and the whole iteration (rollout + GAE +
 update). Host clock around work that ends in a device synchronise; both trainers are warmed up first.
 Medians only: no kernel trace is taken. Writes profiles/<name>/bench_<name>.txt and .json, <name>
-being pendulum, cartpole, reacher, quadrotor or cheetah.
+being pendulum, cartpole, reacher, quadrotor, acrobot or cheetah.
 
   python scripts/bench_device_env.py --env_id ID [--num_envs 4096] [--num_steps 128] [--reps 10] [--out DIR]
 """
@@ -22,7 +22,7 @@ import numpy as np  # noqa: E402
 import ppo_amd  # noqa: E402
 
 SHORT = {"Pendulum-v1": "pendulum", "CartPoleContinuous-v1": "cartpole", "ReacherPlanar-v0": "reacher",
-         "QuadrotorHover-v0": "quadrotor", "HalfCheetah-v5": "cheetah"}
+         "QuadrotorHover-v0": "quadrotor", "AcrobotContinuous-v1": "acrobot", "HalfCheetah-v5": "cheetah"}
 
 
 def main():
