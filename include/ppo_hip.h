@@ -130,6 +130,15 @@ int ppo_create(const ppo_hip_config* cfg, int device, ppo_t** out);
  *                            workgroup, MFMA) or k_rollout_v (2 envs per workgroup, VALU; O <= 32);
  *                            auto: k_rollout_v at E <= 512. Bitwise the same results. valu on an
  *                            agent it cannot serve (the PPO agent, O > 32, device env wrappers) fails
+ *   rollout_kernel=split     the same agent's rollout on k_rollout_s (2 envs per workgroup, VALU, the
+ *                            layers' k range split over wave halves, W2 register-resident): opt-in, never
+ *                            auto's choice; steps every device env kind (Pendulum, CartPole, Reacher,
+ *                            Quadrotor, Acrobot and the synthetic cheetah). Its sums are reassociated: the
+ *                            results are NOT bitwise those of the other two kernels (they meet the fp64
+ *                            oracle's bars; the env arithmetic stays bitwise); deterministic run to run.
+ *                            Fails where it cannot run: at create for the PPO agent, O > 32 or
+ *                            rollout=per_step; in ppo_rollout_synth for more than 8 actions or an env
+ *                            with device env wrappers
  *   gae=auto|serial|scan     GAE as the reference's serial recurrence per env (k_gae: bit-exact with
  *                            ppo:447-467, ac:759-779) or as a segmented scan over the steps (k_gae_scan: 16
  *                            segments per 64 envs, within 1e-5 of the serial form and of the golden

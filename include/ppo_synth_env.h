@@ -17,7 +17,7 @@
  * The vector-env semantics, the episode statistics and the wrapper chain are the same for both kinds.
  * Its state q [E, 3] holds theta, thetadot and one unused slot. The dynamics clip the torque to
  * [-2, 2] themselves, whatever psyn_set_action_space says. Not covered for this kind: the VALU
- * rollout kernel (rollout_kernel=valu is refused).
+ * rollout kernel (rollout_kernel=valu is refused; rollout_kernel=split serves this kind).
  *
  * A third kind, PSYN_CARTPOLE (psyn_create_env("CartPoleContinuous-v1")), is the first whose episodes
  * terminate: Gymnasium's CartPole-v1 with the force 10 * clip(a, -1, 1) from one continuous action
@@ -27,7 +27,7 @@
  * step's termination flag reaches NormalizeReward (the return accumulator restarts after a
  * termination, not after a truncation); done = terminated or truncated, and psyn_step still returns
  * done only. Episodes end on any step, on different steps in different envs. rollout_kernel=valu is
- * refused for this kind as well.
+ * refused for this kind as well (rollout_kernel=split serves this kind).
  *
  * A fourth kind, PSYN_REACHER (psyn_create_env("ReacherPlanar-v0")), is the first real task with a
  * two-dimensional action: a two-link planar arm, O = 10, A = 2, action space [-1, 1] per dimension,
@@ -38,7 +38,7 @@
  * holds q1, q2, q1dot, q2dot, gx, gy and four unused slots. The goal (gx, gy) is env state that no step
  * touches: it survives every step and is redrawn at every autoreset. The dynamics clip both actions to
  * [-1, 1] themselves; the termination flag passed to the wrapper chain is always 0. Not covered for
- * this kind: the VALU rollout kernel (rollout_kernel=valu is refused).
+ * this kind: the VALU rollout kernel (rollout_kernel=valu is refused; rollout_kernel=split serves this kind).
  *
  * A fifth kind, PSYN_QUADROTOR (psyn_create_env("QuadrotorHover-v0")), is the first real task wider
  * than one 16-wide input tile: a rigid-body quadrotor hovering at the origin, O = 18, A = 4, action
@@ -48,7 +48,7 @@
  * Its state q [E, 18] holds p, v, the unit quaternion (w, x, y, z), omega and five unused slots. The
  * dynamics clip the four actions to [-1, 1] themselves; the termination flag reaches the wrapper
  * chain as CartPole's does. Not covered for this kind: the VALU rollout kernel (rollout_kernel=valu
- * is refused).
+ * is refused; rollout_kernel=split serves this kind).
  *
  * A sixth kind, PSYN_ACROBOT (psyn_create_env("AcrobotContinuous-v1")), is the first whose step is a
  * multi-stage integrator: Gymnasium's Acrobot-v1 ("book" dynamics, one RK4 step of 0.2 s per env step)
@@ -58,7 +58,8 @@
  * include/ppo_acrobot.h — bit for bit the host env ppo.cpp_amd/gymcpp/acrobot.h. Its state q [E, 6]
  * holds theta1, theta2, theta1dot, theta2dot and two unused slots. Termination here is success: a
  * shorter episode is the better one, and the termination flag reaches the wrapper chain as
- * CartPole's does. rollout_kernel=valu is refused for this kind as well.
+ * CartPole's does. rollout_kernel=valu is refused for this kind as well (rollout_kernel=split
+ * serves this kind).
  */
 #ifndef PPO_SYNTH_ENV_H
 #define PPO_SYNTH_ENV_H

@@ -175,7 +175,7 @@ struct ppo_ctx {
   float* LNS[2] = {nullptr, nullptr};
   int upd32_mix = 0;       // k_upd32 with the actor trunk on k_upd's body (upd_mfma=mix)
   bool use_upd2 = false;  // two-trunk k_upd2 (ppo_update_narrow.hip, H = 64 tanh agent)
-  int rollout_kernel = 0;   // AC persistent rollout: 0 auto, 1 k_rollout (MFMA), 2 k_rollout_v (VALU)
+  int rollout_kernel = 0;   // AC persistent rollout: 0 auto, 1 k_rollout (MFMA), 2 k_rollout_v (VALU), 3 k_rollout_s
   int upd2_split = 0;       // k_l1g (layer 1 as a gathered GEMM into Z1) + k_upd2's split form at 2 / 3 per CU
   float* Z1 = nullptr;      // [Mr][128] layer-1 pre-activations of the minibatch (split form)
   UpdGeoOut upd = {};
@@ -314,7 +314,7 @@ struct CreateOptions {
   // 1: ppo_update replays its minibatch launches as one captured hipGraph; 0 (default): eager.
   // Snapshots work with it on (ppo_read_snapshot waits for the snapshot's event on the host).
   int update_graph = -1;  // -1 auto (kUpdGraphAutoRows), 0 eager, 1 graph
-  int rollout_kernel = 0;  // 0 auto, 1 mfma (k_rollout), 2 valu (k_rollout_v)
+  int rollout_kernel = 0;  // 0 auto, 1 mfma (k_rollout), 2 valu (k_rollout_v), 3 split (k_rollout_s)
   int upd2_split = -1;  // -1 auto (= kUpd2SplitAuto: the single k_upd2), 0 one k_upd2, 2 / 3 split at 2 / 3 workgroups per CU
   int upd_mfma = 0;     // 0 auto (bx6 where it applies, else 16), 16: k_upd (16x16x4 fp32 MFMAs),
                         // 32: k_upd32 (32x32x2; LayerNorm-Beta agent, H = 256),
@@ -395,8 +395,8 @@ static int parse_create_options(const char* opts, CreateOptions* o) {
     else if (k == "dw_mfma" && (v == "auto" || v == "f32" || v == "bf16x9" || v == "bf16x8" || v == "bf16x6"))
       o->dw_bx = v == "auto" ? -1 : v == "f32" ? 0 : v == "bf16x9" ? 9 : v == "bf16x8" ? 8 : 6;
     else if (k == "update_graph" && (v == "auto" || v == "0" || v == "1")) o->update_graph = v == "auto" ? -1 : v[0] - '0';
-    else if (k == "rollout_kernel" && (v == "auto" || v == "mfma" || v == "valu"))
-      o->rollout_kernel = v == "auto" ? 0 : v == "mfma" ? 1 : 2;
+    else if (k == "rollout_kernel" && (v == "auto" || v == "mfma" || v == "valu" || v == "split"))
+      o->rollout_kernel = v == "auto" ? 0 : v == "mfma" ? 1 : v == "valu" ? 2 : 3;
     else if (k == "upd2_split" && (v == "auto" || v == "0" || v == "2" || v == "3")) o->upd2_split = v == "auto" ? -1 : v[0] - '0';
     else if (k == "upd_mfma" && (v == "auto" || v == "16" || v == "32" || v == "mix" || v == "bx6"))
       o->upd_mfma = v == "auto" ? 0 : v == "mix" ? 1 : v == "bx6" ? 6 : atoi(v.c_str());
@@ -474,6 +474,14 @@ extern "C" int ppo_create_ex(const ppo_hip_config* cfg, int device, const char* 
   if (opt.rollout_kernel == 2 && (cfg->net_kind != PPO_NET_LN_BETA || c->K.OP > 32)) {
     delete c;  // nothing allocated yet
     return fail("ppo_create: rollout_kernel=valu needs the LayerNorm-Beta agent with obs_dim <= 32");
+  }
+  if (opt.rollout_kernel == 3 && (cfg->net_kind != PPO_NET_LN_BETA || c->K.OP > 32)) {
+    delete c;
+    return fail("ppo_create: rollout_kernel=split needs the LayerNorm-Beta agent with obs_dim <= 32");
+  }
+  if (opt.rollout_kernel == 3 && opt.rollout != PPO_ROLLOUT_AUTO) {
+    delete c;  // k_rollout_s is a persistent kernel: with rollout=per_step it would never run
+    return fail("ppo_create: rollout_kernel=split needs the persistent rollout (rollout=auto, not per_step)");
   }
   int upd_kernel = opt.upd_kernel;
 #ifdef PPO_DIAG
@@ -1566,7 +1574,8 @@ extern "C" int ppo_kernel_info(const ppo_t* c, char* buf, int len) {
   const std::string vals = rollout_supported(c->K) != 0 ? "k_act" : c->values_bx ? "k_vbx/bx6"
                            : c->K.kind == PPO_NET_TANH_NORMAL ? "k_values4/f32" : "k_values/f32";
   const std::string s = "update=" + upd + " dw=" + dw + " values=" + vals +
-                        (c->gn_fold && !c->gradstep ? " norm=k_colsum" : c->gradstep ? " norm=k_gradstep" : " norm=k_gradnorm");
+                        (c->gn_fold && !c->gradstep ? " norm=k_colsum" : c->gradstep ? " norm=k_gradstep" : " norm=k_gradnorm") +
+                        (c->rollout_kernel == 3 ? " rollout=k_rollout_s" : "");  // the opt-in rollout kernel (create and ppo_rollout_synth refuse what would bypass it)
   snprintf(buf, (size_t)len, "%s", s.c_str());
   return 0;
 }
@@ -1771,6 +1780,8 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
   // runs k_act4's arithmetic (the per-step path's kernel at O >= 112, or with act_kernel=4)
   const bool persistent = c->rollout_mode == PPO_ROLLOUT_AUTO && rollout_supported(c->K) == 0 &&
                           (c->K.kind == PPO_NET_TANH_NORMAL || !env->a.w.on);
+  if (c->rollout_kernel == 3 && !persistent)  // an explicit kernel that cannot run is an error, not a silent per-step path
+    return fail("ppo_rollout_synth: rollout_kernel=split needs the persistent rollout: at most 8 actions, no device env wrappers");
   if (persistent) {
     // one persistent launch for all T steps (k_rollout), then the critic over the stored rows
     RolloutArgs r;
@@ -1805,6 +1816,8 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
                                             "kind is ") + psyn_kind_name(env->a.kind) + ": use rollout_kernel=auto or mfma"
                     : lrc == -3 ? "ppo_rollout_synth: rollout_kernel=valu needs the LayerNorm-Beta agent, O <= 32 and no "
                                 "device env wrappers"
+                    : lrc == -5 ? "ppo_rollout_synth: rollout_kernel=split needs the LayerNorm-Beta agent, O <= 32, at most "
+                                "8 actions and no device env wrappers"
                               : "ppo_rollout_synth: rollout kernel launch failed");
       if (r.s_beta) launch_beta_logp(r.s_beta, c->buf[PPO_BUF_LOGPROBS], (long)E * c->cfg.num_steps, c->K.A, c->stream);
     }

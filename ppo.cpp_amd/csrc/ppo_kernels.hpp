@@ -290,7 +290,8 @@ struct RolloutArgs {
   float* s_beta;        // AC: [T][E][A][3] (alpha, beta, sample) for k_beta_logp; null: log-probs in the loop
   SynthArgs env;
   float lo, hi;         // the env's action space (clip_actions)
-  int variant;          // AC rollout kernel: 0 auto, 1 k_rollout (MFMA, 16 envs per workgroup), 2 k_rollout_v (VALU)
+  int variant;          // AC rollout kernel: 0 auto, 1 k_rollout (MFMA, 16 envs per workgroup), 2 k_rollout_v (VALU),
+                        // 3 k_rollout_s (VALU, k split over wave halves; any device env kind)
 };
 // Critic forward over n stored rows (ppo_rollout.hip, k_values): values[i] = critic(obs[i]), the
 // same chain as k_act3's critic workgroups, so each value is bitwise the one the per-step act
@@ -331,6 +332,7 @@ void launch_eval_record(const SynthArgs& env, const float* done, int nE, long lo
 int launch_vbx(const ValuesArgs& a, hipStream_t s);  // ppo_update.hip; -1 when the shape is not covered
 int rollout_supported(const PackedLayout& K);
 int launch_rollout(const RolloutArgs& a, hipStream_t s);
+int launch_rollout_s(const RolloutArgs& a, hipStream_t s);  // ppo_rollout_split.hip (variant 3); -5 when it cannot apply
 int launch_values(const ValuesArgs& a, hipStream_t s);
 int launch_beta_logp(const float* s_beta, float* logp, long n, int A, hipStream_t s);
 

@@ -14,6 +14,8 @@
 //  * k_rollout_v (AC agent, E <= 512): 2 envs per workgroup on the VALU, each layer output one
 //    fmaf chain in the MFMA's k order, so bitwise k_rollout's results.
 //  * k_rollout4 / k_values4: the same for the 64-wide PPO agent (k_act4's arithmetic).
+//  * k_rollout_s (ppo_rollout_split.hip; opt-in): 2 envs per workgroup on the VALU with the k range
+//    split over wave halves, every device env kind; not bitwise the others (DESIGN §3b').
 // They use the building blocks of k_act3 (ppo_act_common.hpp) in the same order: every action,
 // log-prob, value, reward and observation is bitwise the one the per-step path produces
 // (tests/test_gpu_rollout.py).
@@ -830,14 +832,6 @@ template <int K>
 PPO_DEV void fmac_bc(float& acc, float x, float w) {
   asm volatile("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(w), "n"(K));
 }
-template <int... Is, typename F>
-PPO_DEV void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, typename F>
-PPO_DEV void static_for(F&& f) {
-  static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 }  // namespace
 
 constexpr int kRVThreads = 512;
@@ -1197,7 +1191,8 @@ static int launch_rollout_v_t(const RolloutArgs& a, hipStream_t s) {
 
 // the VALU rollout where it applies: AC agent, O <= 32, and few envs (auto: E <= 512, the N = 8
 // shard of the metric config); a.variant 1 forces k_rollout, 2 k_rollout_v. k_rollout_v steps the
-// synthetic cheetah only: a Pendulum, CartPole, Reacher or Quadrotor env never takes it.
+// synthetic cheetah only: a Pendulum, CartPole, Reacher or Quadrotor env never takes it (a.variant 3,
+// k_rollout_s of ppo_rollout_split.hip, serves them).
 static bool use_rollout_v(const RolloutArgs& a) {
   if (a.env.kind != PSYN_CHEETAH) return false;
   if (a.K.kind != PPO_NET_LN_BETA || a.K.OP > 32 || a.env.w.on || !a.s_beta || a.variant == 1) return false;
@@ -1206,6 +1201,7 @@ static bool use_rollout_v(const RolloutArgs& a) {
 
 int launch_rollout(const RolloutArgs& a, hipStream_t s) {
   if (rollout_supported(a.K) != 0) return -1;
+  if (a.variant == 3) return launch_rollout_s(a, s);  // rollout_kernel=split: k_rollout_s, any env kind (-5: cannot apply)
   // an explicit rollout_kernel=valu that cannot apply is an error, not a silent k_rollout
   if (a.variant == 2 && a.env.kind != PSYN_CHEETAH) return -4;
   if (a.variant == 2 && !use_rollout_v(a)) return -3;

@@ -15,6 +15,7 @@
 #include "ppo_env_kinds.hpp"
 
 #include <type_traits>
+#include <utility>
 
 #ifndef ROLL_STAMP
 #define ROLL_STAMP(t, k) do {} while (0)
@@ -25,6 +26,17 @@ namespace {
 using namespace act;
 
 constexpr int kRows = 16;  // envs (rows) per workgroup
+
+// f(std::integral_constant<int, i>{}) for i = 0 .. N-1, unrolled: the index is a compile-time constant
+// inside f (an immediate operand of inline asm, k_rollout_v / k_rollout_s)
+template <int... Is, typename F>
+PPO_DEV void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
+  (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, typename F>
+PPO_DEV void static_for(F&& f) {
+  static_for_impl(std::make_integer_sequence<int, N>{}, f);
+}
 
 template <int NTO, int NHT, int ROWS = kRows>
 struct RollGeo {

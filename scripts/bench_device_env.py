@@ -8,7 +8,11 @@ update). Host clock around work that ends in a device synchronise; both trainers
 Medians only: no kernel trace is taken. Writes profiles/<name>/bench_<name>.txt and .json, <name>
 being pendulum, cartpole, reacher, quadrotor, acrobot or cheetah.
 
+--options gives the persistent trainer create options (rollout_kernel=split: k_rollout_s), --tag a suffix
+of the output files' names.
+
   python scripts/bench_device_env.py --env_id ID [--num_envs 4096] [--num_steps 128] [--reps 10] [--out DIR]
+                                     [--options OPTS] [--tag TAG]
 """
 import argparse
 import json
@@ -32,18 +36,21 @@ def main():
     ap.add_argument("--num_steps", type=int, default=128)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--options", default=None)
+    ap.add_argument("--tag", default="")
     a = ap.parse_args()
     name = SHORT[a.env_id]
     out = a.out or os.path.join(ROOT, "profiles", name)
     E, T = a.num_envs, a.num_steps
     cfg = ppo_amd.ACPPOConfig(env_id=a.env_id, num_envs=E, num_steps=T, total_timesteps=E * T * (4 * a.reps + 8))
-    trs = {"persistent": ppo_amd.Trainer(cfg), "per_step": ppo_amd.Trainer(cfg, options="rollout=per_step")}
+    trs = {"persistent": ppo_amd.Trainer(cfg, options=a.options), "per_step": ppo_amd.Trainer(cfg, options="rollout=per_step")}
     lines = []
 
     def say(s):
         print(s, flush=True)
         lines.append(s)
 
+    say(f"persistent trainer: options {a.options}, {trs['persistent'].agent.kernel_info()}")
     say(f"AC agent, {a.env_id} device env, E={E} T={T}: {E * T} env steps per rollout; {a.reps} alternating repetitions")
     for tr in trs.values():  # warm-up: code objects, first launches, the update's graph capture
         for _ in range(3):
@@ -85,8 +92,8 @@ def main():
     for t in trs.values():
         t.close()
     os.makedirs(out, exist_ok=True)
-    open(os.path.join(out, f"bench_{name}.txt"), "w").write("\n".join(lines) + "\n")
-    json.dump(res, open(os.path.join(out, f"bench_{name}.json"), "w"), indent=1)
+    open(os.path.join(out, f"bench_{name}{a.tag}.txt"), "w").write("\n".join(lines) + "\n")
+    json.dump(res, open(os.path.join(out, f"bench_{name}{a.tag}.json"), "w"), indent=1)
 
 
 if __name__ == "__main__":
