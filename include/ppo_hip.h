@@ -112,8 +112,9 @@ int ppo_create(const ppo_hip_config* cfg, int device, ppo_t** out);
  *                            once the context has taken a snapshot: the CLIs read snapshots from a writer thread)
  *                            hipGraph captured on the second call (one process, gradstep=split,
  *                            no profiling); the Adam step constants come from a device table, so
- *                            the result is bitwise the eager one. Checkpoint snapshots work with it
- *                            (ppo_read_snapshot waits on the host, never across streams)
+ *                            the result is bitwise the eager one. With checkpoint snapshots: auto stays
+ *                            eager from the first ppo_snapshot_state on; 1 keeps the graph, and is for
+ *                            callers that take and read snapshots on the thread that updates
  *   upd2_split=auto|0|2|3    64-wide agent with wide inputs (O % 4 == 0, OP = 384: Humanoid): layer 1
  *                            of both trunks as one gathered GEMM (k_l1g) and k_upd2's tail in its own
  *                            launch at 2 / 3 workgroups per CU, or the single k_upd2 (0; auto: the
@@ -237,8 +238,9 @@ int ppo_debug_last_grad(ppo_t* ctx, float* host, long n);
  * parameters and the Adam state on the context stream (ordered after the last update, before the
  * next) and returns at once; ppo_read_snapshot, callable from another host thread, waits (on the
  * host, hipEventSynchronize) for that copy only and unpacks it in the flat reference order — no
- * cross-stream dependency, so it is safe while the context stream is being captured into a hipGraph
- * (update_graph=1). One snapshot buffer: call
+ * cross-stream dependency. A reader thread next to an update that captures the context stream into
+ * its hipGraph still made the capture fail: update_graph=auto therefore stays eager once a snapshot
+ * exists, and update_graph=1 is for single-threaded callers. One snapshot buffer: call
  * ppo_read_snapshot before the next ppo_snapshot_state. */
 int ppo_snapshot_state(ppo_t* ctx);
 int ppo_read_snapshot(ppo_t* ctx, float* params_host, float* m_host, float* v_host, long n, long* step);

@@ -13,7 +13,7 @@
 // host, one row each, and dispatch_env_kind turns a run-time kind into the compile-time one.
 // Used by the per-step env kernels k_env_reset / k_env_step (ppo_kernels.hip), by env_lane_step
 // (ppo_rollout_common.hpp) inside the persistent kernels k_rollout, k_rollout4 (ppo_rollout.hip) and
-// k_eval (ppo_eval.hip), and by the C API (ppo_capi.hip).
+// k_eval (ppo_eval.hip), and by the C API (ppo_capi_env.hip).
 // PSYN_CHEETAH has no DevEnv: it exists at any (O, A) and its step is spread over an env's lanes
 // (k_synth_step / k_synth_step_wide, chee_lanes_step of ppo_rollout_common.hpp, k_rollout4's element
 // loop). Its arithmetic is include/ppo_cheetah.h, shared with the host env

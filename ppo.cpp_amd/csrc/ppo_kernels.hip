@@ -1124,7 +1124,7 @@ __global__ __launch_bounds__(512) void k_dwf_dma(DwArgs a) {
 
 // =============================================================================================
 // k_dwf_bx — k_dwf_dma's products on BF16 MFMAs with every fp32 operand split exactly in three
-// (create option dw_mfma=bf16x9 / bf16x8; the default: see ppo_capi.hip).
+// (create option dw_mfma=bf16x9 / bf16x8; the default: see ppo_capi_plan.hip).
 //
 // On gfx950 the fp32 MFMA runs at 1/16 of the BF16 rate (MI355X_MICROARCH.md: 157 vs ~2 500
 // TF/s), and k_dwf_dma is MFMA-bound (matrix pipe 0.77 busy, 1.9 VALU per MFMA). Every fp32 x is

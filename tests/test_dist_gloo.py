@@ -1,5 +1,5 @@
 """world_size-2 data-parallel update over gloo on the CPU — the exchange pattern ppo_update runs
-over RCCL on the GPU (ppo.cpp_amd/csrc/ppo_capi.hip), with the oracle as the per-rank compute:
+over RCCL on the GPU (ppo.cpp_amd/csrc/ppo_capi_update.hip), with the oracle as the per-rank compute:
 
   * advantage stats: mean all-reduced with averaging, sum of squares all-reduced with summing,
     std with Bessel's correction over world*M_local (ac_ppo_continuous_action.cpp:830-849);

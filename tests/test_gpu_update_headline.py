@@ -363,7 +363,7 @@ def test_upd2_bx6_is_as_accurate_as_fp32_mfma(E, T):
 
 @pytest.mark.parametrize("E,T,O_", [(4096, 32, 17), (3999, 4, 17), (512, 32, 16), (700, 9, 11), (1024, 8, 20)])
 def test_h1_recompute_is_bitwise_the_stored_h1(E, T, O_):
-    """h1_handoff=recompute (the default where it applies): k_upd writes each row's layer-1 LayerNorm
+    """h1_handoff=recompute (opt-in; h1_handoff=store is the default): k_upd writes each row's layer-1 LayerNorm
     statistics (8 bytes) instead of its 1 KB H1 row, and k_dwf_bx recomputes H1 per 16-row stage from
     the staged Xn rows with k_upd's own layer-1 chain (W1 swizzled copy, bias init, the same 16x16x4 fp32
     MFMA k order and last-block k-steps, the same LayerNorm affine + ReLU expression). Against
