@@ -138,7 +138,18 @@ int ppo_set_rollout_mode(struct ppo_ctx* ctx, int mode);
  * hidden 256, obs_dim <= 32, act_dim <= 8) on an env without wrappers a chunk is one persistent launch
  * (k_eval: actor weights resident in registers, the env step fused in); otherwise, and with mode = 1,
  * it is chunk_steps x {act launch, psyn_step, event recorder}. Both give bitwise the same result.
- * ppo_eval_info reports the path the last call took ("eval=k_eval" | "eval=per_step" | "eval=none").
+ *
+ * mode = 2 is "persistent or refuse". It takes k_eval where mode = 0 takes it, and k_eval4 for the PPO
+ * agent (tanh-Normal, hidden 64, act_dim <= 32, obs_dim padded to 16, 32, 112 or 384) on any env kind,
+ * with the wrapper chain attached or not: one persistent launch per chunk, the actor in registers, the
+ * env step, NormalizeReward and NormalizeObservation fused in, and the env and wrapper state written
+ * back at the end of each chunk. Any other agent / env is refused (-1; the message names the agent
+ * kind, OP and act_dim), never run per step. mode = 0 does not take k_eval4. k_eval4 runs the act
+ * kernel k_act4's arithmetic: on a context created with act_kernel=4 (the default at obs_dim >= 112)
+ * mode = 2 and mode = 1 return the same bits and leave the same env and wrapper state; on a context
+ * with another act kernel the two may differ by the act kernels' summation order.
+ * ppo_eval_info reports the path the last call took ("eval=k_eval" | "eval=k_eval4" | "eval=per_step" |
+ * "eval=none").
  *
  * Refused (-1, ppo_last_error) before any launch: NULL arguments, num_eval_runs <= 0, num_eval_envs
  * outside [1, E], cap < num_eval_runs + num_eval_envs - 1, PPO_GIVEN, PPO_ROACH on a tanh-Normal
@@ -152,7 +163,7 @@ typedef struct ppo_eval_config {
   int  num_eval_runs;
   long step0;           /* Philox step id of evaluation step 0 (PPO_SAMPLE only) */
   int  chunk_steps;     /* 0 = default (4096; PSYN_CARTPOLE 512); env steps per launch / per read-out */
-  int  mode;            /* 0 auto, 1 force the per-step path (tests, A/B) */
+  int  mode;            /* 0 auto, 1 force the per-step path (tests, A/B), 2 a persistent kernel or an error */
 } ppo_eval_config;
 
 int ppo_evaluate_synth(struct ppo_ctx* ctx, psyn_t* env, const ppo_eval_config* cfg,

@@ -203,8 +203,8 @@ static EvalArgs base_eval(ppo_t* c) {
 }
 
 // Policy evaluation on the device env (ac:965-1001 with num_eval_envs = 1; ppo:589-626 with all envs).
-// Chunks of env steps run on the context stream, either as one persistent launch each (k_eval) or as
-// chunk x {act, psyn_step, k_eval_record}; after each chunk one read-out of the event buffer (its
+// Chunks of env steps run on the context stream, either as one persistent launch each (k_eval; with
+// mode = 2 also k_eval4, the PPO agent's) or as chunk x {act, psyn_step, k_eval_record}; after each chunk one read-out of the event buffer (its
 // counter in the first record) decides whether another chunk is needed. Both paths produce the same
 // events bit for bit, and the kept list depends on the events only (eval_select), not on the chunks.
 extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* cfg, float* returns_host,
@@ -220,12 +220,23 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
   if (cfg->sample_type < 0 || cfg->sample_type > PPO_ROACH || (cfg->sample_type == PPO_ROACH && c->K.kind != PPO_NET_LN_BETA))
     return fail("Unsupported sample type used. Sample type: " + std::to_string(cfg->sample_type));
   if (O != c->K.O || A != c->K.A) return fail("ppo_evaluate_synth: env shape mismatch");
-  if (cfg->chunk_steps < 0 || (cfg->mode != 0 && cfg->mode != 1)) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
+  if (cfg->chunk_steps < 0 || cfg->mode < 0 || cfg->mode > 2) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
+  // the path (ppo_t::eval_path): auto takes k_eval where it applies and the per-step launches
+  // otherwise; mode = 2 takes a persistent kernel, k_eval or k_eval4, or refuses
+  int path = 2;
+  if (cfg->mode != 1 && eval_supported(c->K) == 0 && !env->a.w.on) path = 1;
+  else if (cfg->mode == 2 && eval4_supported(c->K) == 0) path = 3;
+  else if (cfg->mode == 2)
+    return fail(std::string("ppo_evaluate_synth: mode = 2 (persistent) has no kernel for the ") +
+                (c->K.kind == PPO_NET_LN_BETA ? "LayerNorm-Beta" : "tanh-Normal") + " agent at H = " + std::to_string(c->K.H) +
+                ", OP = " + std::to_string(c->K.OP) + ", A = " + std::to_string(A) +
+                (env->a.w.on ? " on an env with the wrapper chain" : "") +
+                ": k_eval serves LayerNorm-Beta, H = 256, OP <= 32, A <= 8 without wrappers; k_eval4 tanh-Normal, H = 64, "
+                "OP in {16, 32, 112, 384}, A <= 32; use mode = 0 or 1");
   // an env that terminates can finish an episode every other step, so its chunks are shorter by
   // default (the event buffer below is sized for the worst case)
   const bool terminates = psyn_terminates(env);
   const int chunk = cfg->chunk_steps > 0 ? cfg->chunk_steps : (terminates ? 512 : 4096);
-  const bool persistent = cfg->mode == 0 && eval_supported(c->K) == 0 && !env->a.w.on;
   // the env truncates after max_steps (the cheetah CHEE_MAX_STEPS, Pendulum 200) steps and resets on the next one: an env
   // finishes at most one episode per max_steps + 1 steps, which bounds the events of a chunk (an
   // overflow is still detected). CartPoleContinuous-v1 and QuadrotorHover-v0 terminate: an episode is
@@ -254,7 +265,7 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
   size_t keep = 0;
   while (keep == 0) {
     HIP_TRY(hipMemsetAsync(d_ev, 0, sizeof(EvalEvent), s));
-    if (persistent) {
+    if (path != 2) {
       EvalArgs a = base_eval(c);
       a.nE = nE;
       a.T = chunk;
@@ -268,7 +279,7 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
       a.ev = d_ev + 1;
       a.count = d_count;
       a.cap = (int)devcap;
-      if (launch_eval(a, s) != 0) return fail("ppo_evaluate_synth: evaluation kernel launch failed");
+      if ((path == 1 ? launch_eval(a, s) : launch_eval4(a, s)) != 0) return fail("ppo_evaluate_synth: evaluation kernel launch failed");
     } else {
       for (int t = 0; t < chunk; ++t) {
         if (int rc = ppo_get_action_and_value(c, nE, d_obs, cfg->sample_type, nullptr, 0, cfg->step0 + (long)(k + t), d_act,
@@ -293,13 +304,14 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
   }
   *n_out = (int)keep;
   *env_steps_out = (long)stop + 1;
-  c->eval_path = persistent ? 1 : 2;
+  c->eval_path = path;
   return 0;
 }
 
 extern "C" int ppo_eval_info(const ppo_t* c, char* buf, int len) {
   if (!c || !buf || len <= 0) return fail("ppo_eval_info: null argument");
-  snprintf(buf, (size_t)len, "eval=%s", c->eval_path == 1 ? "k_eval" : c->eval_path == 2 ? "per_step" : "none");
+  snprintf(buf, (size_t)len, "eval=%s",
+           c->eval_path == 1 ? "k_eval" : c->eval_path == 2 ? "per_step" : c->eval_path == 3 ? "k_eval4" : "none");
   return 0;
 }
 

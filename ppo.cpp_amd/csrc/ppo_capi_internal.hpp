@@ -224,7 +224,7 @@ struct ppo_ctx {
   hipEvent_t sched_ev[2] = {};          // the H2D copy out of sched_host[i] has completed
   int sched_flip = 0;
   float* beta_store = nullptr;          // persistent AC rollout: (alpha, beta, sample) per (t, env, action)
-  int eval_path = 0;                    // last ppo_evaluate_synth: 0 none yet, 1 k_eval, 2 per-step launches
+  int eval_path = 0;                    // last ppo_evaluate_synth: 0 none yet, 1 k_eval, 2 per-step launches, 3 k_eval4
   // profiling
   unsigned prof_mask = 0;
   std::mutex prof_mu;

@@ -8,6 +8,9 @@
 //    writes in the loop are the episode events. The actor's chain is k_act3's and the env step
 //    k_synth_step's, op for op, so every action, observation and return is bitwise the per-step
 //    path's (ppo_get_action_and_value + psyn_step; tests/test_gpu_eval.py).
+//  * k_eval4 (ppo_eval4.hip): the same for the PPO agent (tanh-Normal, H = 64) on every device env
+//    kind, with the PPO wrapper chain fused in or without it (k_rollout4's geometry and blocks;
+//    opt-in, mode = 2).
 //  * k_eval_record: the per-step path's event recorder, one launch after each psyn_step.
 // Events go to a global buffer through a vector atomic counter, in any order; the host sorts them by
 // (step, env) (ppo_eval_events.hpp).

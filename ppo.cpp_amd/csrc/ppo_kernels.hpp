@@ -305,7 +305,7 @@ struct ValuesArgs {
   long n;
   const float* WBX;     // non-null: the critic's W2 pieces (bx_index): layer 2 as split-bf16 products (k_vbx)
 };
-// Persistent policy evaluation on the device env (ppo_eval.hip, k_eval): one chunk of T env steps of
+// Persistent policy evaluation on the device env (ppo_eval.hip, k_eval / k_eval4): one chunk of T env steps of
 // the envs [0, nE) in one launch, the actor's weights resident in registers; finished episodes are
 // appended to ev through the counter (entries past cap are dropped, the counter still counts them).
 struct EvalArgs {
@@ -327,6 +327,9 @@ struct EvalArgs {
 };
 int eval_supported(const PackedLayout& K);
 int launch_eval(const EvalArgs& a, hipStream_t s);  // -1 when the shape / env is not covered
+// k_eval4, the PPO agent's kernel (H = 64; WSW as for k_rollout4; env.w.on or not; PPO_SAMPLE | PPO_MEAN)
+int eval4_supported(const PackedLayout& K);
+int launch_eval4(const EvalArgs& a, hipStream_t s);  // -1 when the shape / env is not covered
 void launch_eval_record(const SynthArgs& env, const float* done, int nE, long long step, EvalEvent* ev,
                         unsigned* count, int cap, hipStream_t s);
 int launch_vbx(const ValuesArgs& a, hipStream_t s);  // ppo_update.hip; -1 when the shape is not covered

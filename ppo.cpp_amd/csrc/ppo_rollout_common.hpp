@@ -6,6 +6,9 @@
 // parameters, the register-resident weight slices and one trunk forward for the rows in XS. Kernels
 // that use them in the same order produce bitwise identical results (and bitwise k_act3's, whose
 // blocks of ppo_act_common.hpp they are built from).
+// Below them, the blocks of the persistent kernels of the 64-wide tanh-Normal agent, k_rollout4 /
+// k_values4 (ppo_rollout.hip) and k_eval4 (ppo_eval4.hip): the register-resident weights
+// (load4_weights) and the trunk (trunk4: k_act4's arithmetic).
 //
 // A translation unit of the diagnostic stamps build defines ROLL_STAMP / RDBG / kRdbgEnv before it
 // includes this file; without them the hooks compile to nothing.
@@ -13,6 +16,7 @@
 
 #include "ppo_act_common.hpp"
 #include "ppo_env_kinds.hpp"
+#include "ppo_wrap.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -411,6 +415,83 @@ PPO_DEV void load_weight_slices(PBuf wsw, int wave, int lane, f4 (&w1)[NTO][2], 
 #pragma unroll
     for (int t = 0; t < 16; ++t) w2[t][u] = pld4(wsw, l2, 256 * (16 * u + t));
   }
+}
+
+// =============================================================================================
+// The 64-wide tanh-Normal agent's persistent kernels (k_rollout4, k_values4, k_eval4): 256 threads,
+// wave ks holds its K-slice of W1, its tile of W2 and its head tile for the whole launch
+// =============================================================================================
+constexpr int kR4Threads = 256, kR4Rows = 16, kR4H = 64, kR4LDP = kR4Rows + 1, kR4LDH = kR4H + 4;
+
+template <int NTO, int NHT>
+struct Roll4Geo {
+  static constexpr int OP = NTO * 16, NHP = NHT * 16, LDQ = OP + 1;
+};
+
+// this wave's register operands of one trunk, exactly those k_act4 loads at kernel start
+template <int NTO, int NKW>
+PPO_DEV void load4_weights(PBuf wsw, int lane, int ks, f4 (&wa)[NKW][4], f4 (&w2v)[4]) {
+  constexpr int H = kR4H, OP = NTO * 16;
+  const int kb0 = ks * NKW;
+#pragma unroll
+  for (int q = 0; q < NKW; ++q)
+#pragma unroll
+    for (int ft = 0; ft < 4; ++ft) wa[q][ft] = pld4(wsw, 4 * lane, 256 * (ft * NTO + min(kb0 + q, NTO - 1)));
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb) w2v[kb] = pld4(wsw, H * OP + 4 * lane, 256 * (4 * ks + kb));
+}
+
+// k_act4's trunk body for the 16 rows whose inputs this lane holds in xv: layer 1 partials (P1),
+// tanh(b1 + sum of the 4 slices) (H1), layer 2 tile ks, tanh; returns h2 (this wave's tile ks)
+template <int NTO, int NKW, typename PRE_L1>
+PPO_DEV f4 trunk4(const f4 (&xv)[NKW], const f4 (&wa)[NKW][4], const f4 (&w2v)[4], f4 b1, f4 b2,
+                  float (*P1)[kR4H][kR4LDP], float (*H1)[kR4LDH], int ks, int j, int g, PRE_L1 pre_l1) {
+  const int kb0 = ks * NKW;
+  {
+    f4 acc[4];
+#pragma unroll
+    for (int ft = 0; ft < 4; ++ft) acc[ft] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < NKW; ++q) {
+      if (kb0 + q < NTO) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)  // 4 independent chains interleaved, each in its own order
+#pragma unroll
+          for (int ft = 0; ft < 4; ++ft) acc[ft] = mfma16(wa[q][ft][c], xv[q][c], acc[ft]);
+      }
+    }
+    // independent VALU work (the step's Normal draws) issued under the layer-1 MFMAs
+    pre_l1();
+#pragma unroll
+    for (int ft = 0; ft < 4; ++ft)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) P1[ks][16 * ft + 4 * g + r][j] = acc[ft][r];
+  }
+  __syncthreads();
+  {
+    f4 h;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int f = 16 * ks + 4 * g + r;
+      const float z = (((P1[0][f][j] + P1[1][f][j]) + P1[2][f][j]) + P1[3][f][j]) + b1[r];
+      h[r] = tanhf(z);
+    }
+    *reinterpret_cast<f4*>(&H1[j][16 * ks + 4 * g]) = h;
+  }
+  __syncthreads();
+  f4 z2 = b2;
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb) {
+    const f4 hb = *reinterpret_cast<const f4*>(&H1[j][16 * kb + 4 * g]);
+    z2 = mfma16(w2v[kb].x, hb.x, z2);
+    z2 = mfma16(w2v[kb].y, hb.y, z2);
+    z2 = mfma16(w2v[kb].z, hb.z, z2);
+    z2 = mfma16(w2v[kb].w, hb.w, z2);
+  }
+  f4 h2;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) h2[r] = tanhf(z2[r]);
+  return h2;
 }
 
 }  // namespace

@@ -801,12 +801,17 @@ class Agent:
         return buf.value.decode()
 
     def evaluate(self, env: "SynthEnv", num_eval_runs, sample_type=PPO_MEAN, eval_seed=2, num_eval_envs=1, step0=0,
-                 chunk_steps=0, per_step=False):
+                 chunk_steps=0, per_step=False, persistent=False):
         """ppo_evaluate_synth: resets env with eval_seed and runs envs [0, num_eval_envs) with this policy
         until num_eval_runs episodes have finished (all episodes of that step are kept). Returns
         (episodic returns float32[n], episode lengths int32[n], env steps taken); per_step forces the
-        per-step launches (bitwise the same result)."""
-        cfg = EvalConfig(sample_type, eval_seed, num_eval_envs, num_eval_runs, step0, chunk_steps, 1 if per_step else 0)
+        per-step launches (bitwise the same result); persistent asks for one persistent launch per
+        chunk (mode = 2: k_eval, or k_eval4 for the tanh-Normal agent with or without the wrapper
+        chain) and is an error where no such kernel covers the agent."""
+        if per_step and persistent:
+            raise ValueError("evaluate: per_step and persistent are mutually exclusive")
+        cfg = EvalConfig(sample_type, eval_seed, num_eval_envs, num_eval_runs, step0, chunk_steps,
+                         1 if per_step else 2 if persistent else 0)
         cap = max(1, num_eval_runs + num_eval_envs - 1)
         ret, ln = np.zeros(cap, np.float32), np.zeros(cap, np.int32)
         n, steps = C.c_int(), C.c_long()
@@ -815,7 +820,8 @@ class Agent:
         return ret[:n.value].copy(), ln[:n.value].copy(), steps.value
 
     def eval_info(self):
-        """The path the last evaluate() took: "eval=k_eval" | "eval=per_step" | "eval=none" (ppo_eval_info)."""
+        """The path the last evaluate() took: "eval=k_eval" | "eval=k_eval4" | "eval=per_step" | "eval=none"
+        (ppo_eval_info)."""
         buf = C.create_string_buffer(64)
         check(lib().ppo_eval_info(self.h, buf, 64))
         return buf.value.decode()
