@@ -97,6 +97,10 @@ int ppo_create(const ppo_hip_config* cfg, int device, ppo_t** out);
  *   upd_kernel=auto|fwdbwd   minibatch forward/backward: the feature-split k_upd / k_upd2 (auto) or
  *                            the wave-per-16-rows k_fwdbwd
  *   act_kernel=auto|2|4      64-wide agent act: by shape (auto), k_act2, or k_act4
+ *   update=on|off            off: a context that acts and evaluates only (ppo_get_action_and_value,
+ *                            ppo_evaluate_synth); no update kernel is prepared and ppo_update refuses. The
+ *                            default (on) refuses the LayerNorm-Beta agent at hidden 256 from act_dim 13 on
+ *                            (the fused update kernel's LDS); off creates it up to act_dim 20 (Humanoid: 17)
  *   dw_fused=1|0             dW1 / dW2 in one pass (k_dwf) or two (k_dw)
  *   dw_dma=1|0               k_dwf's rows staged by LDS DMA in three buffers (k_dwf_dma, default)
  *                            or through registers in two (k_dwf); bitwise the same

@@ -136,10 +136,12 @@ int ppo_set_rollout_mode(struct ppo_ctx* ctx, int mode);
  * per max_steps + 1 steps, and a PSYN_CARTPOLE env, whose episodes terminate, at most one per 2 steps
  * (num_eval_envs * (chunk_steps / 2 + 2) events of 16 bytes: the reason for its shorter default). For the AC agent (LayerNorm-Beta,
  * hidden 256, obs_dim <= 32, act_dim <= 8) on an env without wrappers a chunk is one persistent launch
- * (k_eval: actor weights resident in registers, the env step fused in); otherwise, and with mode = 1,
+ * (k_eval: actor weights resident in registers, the env step fused in); so it is at Humanoid width
+ * (k_eval_w: obs_dim padded to 384, act_dim 17 .. 24, the cheetah-shaped env without wrappers; W2 resident,
+ * W1 streamed from L2 every step; such a context exists with the create option update=off). Otherwise, and with mode = 1,
  * it is chunk_steps x {act launch, psyn_step, event recorder}. Both give bitwise the same result.
  *
- * mode = 2 is "persistent or refuse". It takes k_eval where mode = 0 takes it, and k_eval4 for the PPO
+ * mode = 2 is "persistent or refuse". It takes k_eval / k_eval_w where mode = 0 takes them, and k_eval4 for the PPO
  * agent (tanh-Normal, hidden 64, act_dim <= 32, obs_dim padded to 16, 32, 112 or 384) on any env kind,
  * with the wrapper chain attached or not: one persistent launch per chunk, the actor in registers, the
  * env step, NormalizeReward and NormalizeObservation fused in, and the env and wrapper state written
@@ -148,7 +150,7 @@ int ppo_set_rollout_mode(struct ppo_ctx* ctx, int mode);
  * kernel k_act4's arithmetic: on a context created with act_kernel=4 (the default at obs_dim >= 112)
  * mode = 2 and mode = 1 return the same bits and leave the same env and wrapper state; on a context
  * with another act kernel the two may differ by the act kernels' summation order.
- * ppo_eval_info reports the path the last call took ("eval=k_eval" | "eval=k_eval4" | "eval=per_step" |
+ * ppo_eval_info reports the path the last call took ("eval=k_eval" | "eval=k_eval_w" | "eval=k_eval4" | "eval=per_step" |
  * "eval=none").
  *
  * Refused (-1, ppo_last_error) before any launch: NULL arguments, num_eval_runs <= 0, num_eval_envs

@@ -214,10 +214,13 @@ extern "C" int ppo_create_ex(const ppo_hip_config* cfg, int device, const char* 
   c->rollout_mode = opt.rollout;
   // from here on a failure has one way out
   int rc = alloc_context(c);
-  if (rc == 0 && fwdbwd_set_lds(c->K, c->plan.lds_bytes) != 0) {
+  if (rc == 0 && !c->plan.no_update && fwdbwd_set_lds(c->K, c->plan.lds_bytes) != 0) {
     (void)hipGetLastError();  // the refusal is reported here: the next call must not find the attribute call's error
     rc = fail("ppo_create: cannot set LDS size for the fused update kernel");
   }
+  // update=off: an update form the planner probed may have been refused its LDS attribute; no kernel of
+  // this context launches it, and the next call must not find that error
+  if (rc == 0 && c->plan.no_update) (void)hipGetLastError();
   if (rc == 0) rc = [] { HIP_TRY(hipDeviceSynchronize()); return 0; }();
   if (rc != 0) {
     ppo_destroy(c);  // leaves the reason (ppo_last_error) as it is

@@ -203,8 +203,8 @@ static EvalArgs base_eval(ppo_t* c) {
 }
 
 // Policy evaluation on the device env (ac:965-1001 with num_eval_envs = 1; ppo:589-626 with all envs).
-// Chunks of env steps run on the context stream, either as one persistent launch each (k_eval; with
-// mode = 2 also k_eval4, the PPO agent's) or as chunk x {act, psyn_step, k_eval_record}; after each chunk one read-out of the event buffer (its
+// Chunks of env steps run on the context stream, either as one persistent launch each (k_eval, or k_eval_w
+// at Humanoid width; with mode = 2 also k_eval4, the PPO agent's) or as chunk x {act, psyn_step, k_eval_record}; after each chunk one read-out of the event buffer (its
 // counter in the first record) decides whether another chunk is needed. Both paths produce the same
 // events bit for bit, and the kept list depends on the events only (eval_select), not on the chunks.
 extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* cfg, float* returns_host,
@@ -221,10 +221,11 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
     return fail("Unsupported sample type used. Sample type: " + std::to_string(cfg->sample_type));
   if (O != c->K.O || A != c->K.A) return fail("ppo_evaluate_synth: env shape mismatch");
   if (cfg->chunk_steps < 0 || cfg->mode < 0 || cfg->mode > 2) return fail("ppo_evaluate_synth: bad chunk_steps / mode");
-  // the path (ppo_t::eval_path): auto takes k_eval where it applies and the per-step launches
-  // otherwise; mode = 2 takes a persistent kernel, k_eval or k_eval4, or refuses
+  // the path (ppo_t::eval_path): auto takes k_eval or k_eval_w where one applies and the per-step
+  // launches otherwise; mode = 2 takes a persistent kernel, k_eval, k_eval_w or k_eval4, or refuses
   int path = 2;
   if (cfg->mode != 1 && eval_supported(c->K) == 0 && !env->a.w.on) path = 1;
+  else if (cfg->mode != 1 && eval_w_supported(c->K) == 0 && !env->a.w.on && env->a.kind == PSYN_CHEETAH) path = 4;
   else if (cfg->mode == 2 && eval4_supported(c->K) == 0) path = 3;
   else if (cfg->mode == 2)
     return fail(std::string("ppo_evaluate_synth: mode = 2 (persistent) has no kernel for the ") +
@@ -279,7 +280,8 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
       a.ev = d_ev + 1;
       a.count = d_count;
       a.cap = (int)devcap;
-      if ((path == 1 ? launch_eval(a, s) : launch_eval4(a, s)) != 0) return fail("ppo_evaluate_synth: evaluation kernel launch failed");
+      if ((path == 1 ? launch_eval(a, s) : path == 4 ? launch_eval_w(a, s) : launch_eval4(a, s)) != 0)
+        return fail("ppo_evaluate_synth: evaluation kernel launch failed");
     } else {
       for (int t = 0; t < chunk; ++t) {
         if (int rc = ppo_get_action_and_value(c, nE, d_obs, cfg->sample_type, nullptr, 0, cfg->step0 + (long)(k + t), d_act,
@@ -311,7 +313,7 @@ extern "C" int ppo_evaluate_synth(ppo_t* c, psyn_t* env, const ppo_eval_config* 
 extern "C" int ppo_eval_info(const ppo_t* c, char* buf, int len) {
   if (!c || !buf || len <= 0) return fail("ppo_eval_info: null argument");
   snprintf(buf, (size_t)len, "eval=%s",
-           c->eval_path == 1 ? "k_eval" : c->eval_path == 2 ? "per_step" : c->eval_path == 3 ? "k_eval4" : "none");
+           c->eval_path == 1 ? "k_eval" : c->eval_path == 2 ? "per_step" : c->eval_path == 3 ? "k_eval4" : c->eval_path == 4 ? "k_eval_w" : "none");
   return 0;
 }
 

@@ -87,6 +87,7 @@ struct KernelPlan {
   int upd_trunk_mask = 3, upd_sched = 1;   // k_upd launch options (PPO_UPD_TRUNK: PPO_DIAG builds only)
   int upd_hot = 0;                      // PPO_UPD2_HOT (PPO_DIAG builds only): UpdArgs::hot
   int dw_fused = 1;
+  bool no_update = false;               // create option update=off: no update kernel is prepared, ppo_update refuses
   int dw_dma = 1;                       // create option dw_dma: k_dwf stages by LDS DMA (k_dwf_dma)
   int dw_bx = 0;                        // create option dw_mfma: 0 fp32 MFMA, 8 / 9 exact bf16 piece products (k_dwf_bx)
   int dw_so = 0;                        // create option dw_stage: k_dwf_bx's split-once form (k_dwf_so)
@@ -103,6 +104,10 @@ struct CreateOptions {
   int upd_kernel = 0;   // 0 auto, 1 the wave-per-16-rows k_fwdbwd
   int act_kernel = 0;   // 0 auto, 2 / 4 force k_act2 / k_act4
   int dw_fused = 1;
+  // update=off: a context that acts and evaluates only. ppo_create does not size the fused update
+  // kernel's LDS, whose 2 A head rows pass 160 KB from A = 13 on at hidden 256 (the refusal of
+  // the default), so the AC agent exists at Humanoid's A = 17; ppo_update refuses.
+  int update = 1;
   int rollout = PPO_ROLLOUT_AUTO;
   // 1: grad norm + Adam in one cooperative launch (k_gradstep); 0 (default): two launches. A
   // cooperative launch costs ~30 us on this stack (measured: cfg1 +8.5 ms per iteration), more
@@ -224,7 +229,7 @@ struct ppo_ctx {
   hipEvent_t sched_ev[2] = {};          // the H2D copy out of sched_host[i] has completed
   int sched_flip = 0;
   float* beta_store = nullptr;          // persistent AC rollout: (alpha, beta, sample) per (t, env, action)
-  int eval_path = 0;                    // last ppo_evaluate_synth: 0 none yet, 1 k_eval, 2 per-step launches, 3 k_eval4
+  int eval_path = 0;                    // last ppo_evaluate_synth: 0 none yet, 1 k_eval, 2 per-step launches, 3 k_eval4, 4 k_eval_w
   // profiling
   unsigned prof_mask = 0;
   std::mutex prof_mu;

@@ -63,6 +63,7 @@ int parse_create_options(const char* opts, CreateOptions* o) {
     if (eq == std::string::npos) return fail("ppo_create_ex: option without '=': " + kv);
     const std::string k = kv.substr(0, eq), v = kv.substr(eq + 1);
     if (k == "upd_kernel" && (v == "auto" || v == "fwdbwd")) o->upd_kernel = v == "fwdbwd";
+    else if (k == "update" && (v == "on" || v == "off")) o->update = v == "on";
     else if (k == "act_kernel" && (v == "auto" || v == "2" || v == "4")) o->act_kernel = v == "auto" ? 0 : v[0] - '0';
     else if (k == "dw_fused" && (v == "0" || v == "1")) o->dw_fused = v[0] - '0';
     else if (k == "rollout" && (v == "auto" || v == "per_step"))
@@ -147,6 +148,7 @@ int plan_kernels(const ppo_hip_config& cfg, const PackedLayout& K, const SmallGr
   p->update_graph = opt.update_graph >= 0 ? opt.update_graph : (M <= kUpdGraphAutoRows ? 1 : 0);
   p->update_graph_auto = opt.update_graph < 0;
   p->rollout_kernel = opt.rollout_kernel;
+  p->no_update = !opt.update;
   if ((opt.rollout_kernel == 2 || opt.rollout_kernel == 3) && (kind != PPO_NET_LN_BETA || OP > 32))
     return fail(std::string("ppo_create: rollout_kernel=") + (opt.rollout_kernel == 2 ? "valu" : "split") +
                 " needs the LayerNorm-Beta agent with obs_dim <= 32");

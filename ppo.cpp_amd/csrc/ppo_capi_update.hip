@@ -387,6 +387,7 @@ extern "C" int ppo_update(ppo_t* c, float lr, const int32_t* perms_dev, ppo_upda
 
 extern "C" int ppo_update_ex(ppo_t* c, float lr, int nsteps, const int32_t* perms_dev, ppo_update_stats* out) {
   if (!c) return fail("ppo_update: null ctx");
+  if (c->plan.no_update) return fail("ppo_update: the context was created with update=off");
   if (nsteps <= 0 || nsteps > c->cfg.num_steps) return fail("ppo_update: bad collected step count");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;

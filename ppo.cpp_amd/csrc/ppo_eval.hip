@@ -8,6 +8,8 @@
 //    writes in the loop are the episode events. The actor's chain is k_act3's and the env step
 //    k_synth_step's, op for op, so every action, observation and return is bitwise the per-step
 //    path's (ppo_get_action_and_value + psyn_step; tests/test_gpu_eval.py).
+//  * k_eval_w (ppo_eval_wide.hip): the same contract at Humanoid width (OP = 384, three head tiles), with a
+//    geometry of its own: W2 resident, W1 streamed every step, one LDS region for XS / HB / HP / ITM.
 //  * k_eval4 (ppo_eval4.hip): the same for the PPO agent (tanh-Normal, H = 64) on every device env
 //    kind, with the PPO wrapper chain fused in or without it (k_rollout4's geometry and blocks;
 //    opt-in, mode = 2).

@@ -330,6 +330,10 @@ int launch_eval(const EvalArgs& a, hipStream_t s);  // -1 when the shape / env i
 // k_eval4, the PPO agent's kernel (H = 64; WSW as for k_rollout4; env.w.on or not; PPO_SAMPLE | PPO_MEAN)
 int eval4_supported(const PackedLayout& K);
 int launch_eval4(const EvalArgs& a, hipStream_t s);  // -1 when the shape / env is not covered
+// k_eval_w (ppo_eval_wide.hip), the AC agent's kernel at Humanoid width: LayerNorm-Beta, H = 256, OP = 384,
+// 33 <= 2 A <= 48, the cheetah-shaped env without wrappers
+int eval_w_supported(const PackedLayout& K);
+int launch_eval_w(const EvalArgs& a, hipStream_t s);  // -1 when the shape / env / mode is not covered
 void launch_eval_record(const SynthArgs& env, const float* done, int nE, long long step, EvalEvent* ev,
                         unsigned* count, int cap, hipStream_t s);
 int launch_vbx(const ValuesArgs& a, hipStream_t s);  // ppo_update.hip; -1 when the shape is not covered

@@ -806,7 +806,7 @@ class Agent:
         until num_eval_runs episodes have finished (all episodes of that step are kept). Returns
         (episodic returns float32[n], episode lengths int32[n], env steps taken); per_step forces the
         per-step launches (bitwise the same result); persistent asks for one persistent launch per
-        chunk (mode = 2: k_eval, or k_eval4 for the tanh-Normal agent with or without the wrapper
+        chunk (mode = 2: k_eval, k_eval_w at Humanoid width, or k_eval4 for the tanh-Normal agent with or without the wrapper
         chain) and is an error where no such kernel covers the agent."""
         if per_step and persistent:
             raise ValueError("evaluate: per_step and persistent are mutually exclusive")
@@ -820,7 +820,7 @@ class Agent:
         return ret[:n.value].copy(), ln[:n.value].copy(), steps.value
 
     def eval_info(self):
-        """The path the last evaluate() took: "eval=k_eval" | "eval=k_eval4" | "eval=per_step" | "eval=none"
+        """The path the last evaluate() took: "eval=k_eval" | "eval=k_eval_w" | "eval=k_eval4" | "eval=per_step" | "eval=none"
         (ppo_eval_info)."""
         buf = C.create_string_buffer(64)
         check(lib().ppo_eval_info(self.h, buf, 64))
