@@ -115,6 +115,17 @@ int ppo_rollout_synth(struct ppo_ctx* ctx, psyn_t* env, float* next_obs_dev, flo
  * env state and episode statistics are then bitwise identical. */
 enum { PPO_ROLLOUT_AUTO = 0, PPO_ROLLOUT_PER_STEP = 1 };
 int ppo_set_rollout_mode(struct ppo_ctx* ctx, int mode);
+/* The AC agent at Humanoid width (hidden 256, obs_dim padded to 384, act_dim 17 .. 24; such a context
+ * exists with the create option update=off) on the cheetah-shaped env without wrappers has a persistent
+ * launch of its own under PPO_ROLLOUT_AUTO (k_rollout_w: W2 resident, W1 streamed from L2 every step, the
+ * five rollout stores through 32-bit buffer offsets), followed by the log-probs and the critic over the
+ * stored rows; bitwise the per-step path. A storage buffer of 4 GiB - 256 B or more (num_steps x num_envs
+ * x max(obs_dim, 3 act_dim) floats) is refused with a message: use fewer envs or steps per context, or
+ * PPO_ROLLOUT_PER_STEP.
+ * ppo_rollout_info reports the path the last ppo_rollout_synth took ("rollout=k_rollout_w" |
+ * "rollout=k_rollout" (also its VALU forms) | "rollout=k_rollout4" | "rollout=per_step" | "rollout=none"
+ * before the first call). */
+int ppo_rollout_info(const struct ppo_ctx* ctx, char* buf, int len);
 
 /* Policy evaluation on the device env: "what return does this policy get"
  * (ac_ppo_continuous_action.cpp:965-1001 with num_eval_envs = 1; ppo_continuous_action.cpp:589-626

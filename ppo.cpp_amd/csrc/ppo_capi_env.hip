@@ -144,6 +144,33 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
                           (c->K.kind == PPO_NET_TANH_NORMAL || !env->a.w.on);
   if (c->plan.rollout_kernel == 3 && !persistent)  // an explicit kernel that cannot run is an error, not a silent per-step path
     return fail("ppo_rollout_synth: rollout_kernel=split needs the persistent rollout: at most 8 actions, no device env wrappers");
+  // the AC agent at Humanoid width (k_rollout_w: OP = 384, 17 <= A <= 24, the cheetah-shaped env, no
+  // wrappers): one persistent launch for all T steps, then the log-probs and the critic over the stored rows
+  if (c->rollout_mode == PPO_ROLLOUT_AUTO && rollout_w_supported(c->K) == 0 && !env->a.w.on && env->a.kind == PSYN_CHEETAH) {
+    const long n = (long)E * c->cfg.num_steps;
+    RolloutArgs r = base_rollout(c);
+    r.next_obs = next_obs;
+    r.next_done = next_done;
+    r.env = env->a;
+    r.lo = lo;
+    r.hi = hi;
+    if (!c->beta_store && dmalloc(&c->beta_store, (size_t)n * c->K.A * 3)) return -2;
+    r.s_beta = c->beta_store;
+    {
+      ProfScope ps(c, PK_ROLLOUT, c->stream);
+      if (const int lrc = launch_rollout_w(r, c->stream))
+        return lrc == -6 ? lrc : fail("ppo_rollout_synth: rollout kernel launch failed");  // -6: launch_rollout_w's message
+      launch_beta_logp(r.s_beta, c->buf[PPO_BUF_LOGPROBS], n, c->K.A, c->stream);
+    }
+    c->values_pending.store(0);  // every stored row's value comes from this pass
+    // k_values (run_values) serves rollout_supported's set, which ends at OP = 112: at this width the critic
+    // of the stored rows is k_act3's critic workgroups, one launch over all T E rows. It is the kernel the
+    // per-step path's values come from, and a row's value does not depend on the rows beside it.
+    if (int rc = ppo_get_value(c, (int)n, c->buf[PPO_BUF_OBS], c->buf[PPO_BUF_VALUES], c->stream)) return rc;
+    HIP_TRY(hipGetLastError());
+    c->rollout_path = 4;
+    return 0;
+  }
   if (persistent) {
     // one persistent launch for all T steps (k_rollout), then the critic over the stored rows
     RolloutArgs r = base_rollout(c);
@@ -172,6 +199,7 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
     if (run_values(c, c->buf[PPO_BUF_OBS], c->buf[PPO_BUF_VALUES], (long)E * c->cfg.num_steps, c->stream) != 0)
       return fail("ppo_rollout_synth: values kernel launch failed");
     HIP_TRY(hipGetLastError());
+    c->rollout_path = c->K.kind == PPO_NET_LN_BETA ? 1 : 3;
     return 0;
   }
   for (int t = 0; t < c->cfg.num_steps; ++t) {
@@ -186,6 +214,15 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
   }
   if (int rc = flush_values(c, c->stream)) return rc;  // the rollout's values, as the persistent path leaves them
   HIP_TRY(hipGetLastError());
+  c->rollout_path = 2;
+  return 0;
+}
+
+extern "C" int ppo_rollout_info(const ppo_t* c, char* buf, int len) {
+  if (!c || !buf || len <= 0) return fail("ppo_rollout_info: null argument");
+  snprintf(buf, (size_t)len, "rollout=%s",
+           c->rollout_path == 1 ? "k_rollout" : c->rollout_path == 2 ? "per_step" : c->rollout_path == 3 ? "k_rollout4"
+           : c->rollout_path == 4 ? "k_rollout_w" : "none");
   return 0;
 }
 

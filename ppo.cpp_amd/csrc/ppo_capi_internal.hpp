@@ -229,6 +229,7 @@ struct ppo_ctx {
   hipEvent_t sched_ev[2] = {};          // the H2D copy out of sched_host[i] has completed
   int sched_flip = 0;
   float* beta_store = nullptr;          // persistent AC rollout: (alpha, beta, sample) per (t, env, action)
+  int rollout_path = 0;                 // last ppo_rollout_synth: 0 none yet, 1 k_rollout (or _v / _s), 2 per-step launches, 3 k_rollout4, 4 k_rollout_w
   int eval_path = 0;                    // last ppo_evaluate_synth: 0 none yet, 1 k_eval, 2 per-step launches, 3 k_eval4, 4 k_eval_w
   // profiling
   unsigned prof_mask = 0;

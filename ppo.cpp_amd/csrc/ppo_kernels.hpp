@@ -340,6 +340,12 @@ int launch_vbx(const ValuesArgs& a, hipStream_t s);  // ppo_update.hip; -1 when 
 int rollout_supported(const PackedLayout& K);
 int launch_rollout(const RolloutArgs& a, hipStream_t s);
 int launch_rollout_s(const RolloutArgs& a, hipStream_t s);  // ppo_rollout_split.hip (variant 3); -5 when it cannot apply
+// k_rollout_w (ppo_rollout_wide.hip), the AC agent's rollout at Humanoid width: eval_w_supported's set, the
+// cheetah-shaped env without wrappers, s_beta set (log-probs by k_beta_logp after the launch)
+int rollout_w_supported(const PackedLayout& K);
+// -1 when the shape / env is not covered, -2 the LDS attribute, -6 (ppo_fail's message) a rollout buffer
+// whose bytes do not fit the kernel's 32-bit store offsets
+int launch_rollout_w(const RolloutArgs& a, hipStream_t s);
 int launch_values(const ValuesArgs& a, hipStream_t s);
 int launch_beta_logp(const float* s_beta, float* logp, long n, int A, hipStream_t s);
 

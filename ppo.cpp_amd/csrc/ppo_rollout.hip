@@ -16,6 +16,8 @@
 //  * k_rollout4 / k_values4: the same for the 64-wide PPO agent (k_act4's arithmetic).
 //  * k_rollout_s (ppo_rollout_split.hip; opt-in): 2 envs per workgroup on the VALU with the k range
 //    split over wave halves, every device env kind; not bitwise the others (DESIGN §3b').
+//  * k_rollout_w (ppo_rollout_wide.hip): k_rollout's contract at Humanoid width (OP = 384, 17 <= A <= 24),
+//    W1 streamed from L2 every step, the rollout stores through buffer resources.
 // They use the building blocks of k_act3 (ppo_act_common.hpp) in the same order: every action,
 // log-prob, value, reward and observation is bitwise the one the per-step path produces
 // (tests/test_gpu_rollout.py).

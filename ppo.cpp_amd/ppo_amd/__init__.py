@@ -229,6 +229,7 @@ SYMBOLS = [
     ("ppo_rollout_synth", _I, [_VP, _VP, _FP, _FP, _FP, _FP]),
     ("ppo_evaluate_synth", _I, [_VP, _VP, C.POINTER(EvalConfig), _FP, _VP, _I, C.POINTER(_I), C.POINTER(_L)]),
     ("ppo_eval_info", _I, [_VP, C.c_char_p, _I]),
+    ("ppo_rollout_info", _I, [_VP, C.c_char_p, _I]),
     ("psyn_set_action_space", _I, [_VP, _F, _F]),
     ("ppo_set_rollout_mode", _I, [_VP, _I]),
     ("psyn_action_space", _I, [_VP, C.POINTER(_F), C.POINTER(_F)]),
@@ -829,6 +830,13 @@ class Agent:
     def set_rollout_mode(self, per_step: bool):
         """ppo_rollout_synth: one persistent launch (default, where supported) or per-step launches."""
         check(lib().ppo_set_rollout_mode(self.h, 1 if per_step else 0))
+
+    def rollout_info(self):
+        """The path the last ppo_rollout_synth took: "rollout=k_rollout_w" | "rollout=k_rollout" | "rollout=k_rollout4" |
+        "rollout=per_step" | "rollout=none" (ppo_rollout_info)."""
+        buf = C.create_string_buffer(64)
+        check(lib().ppo_rollout_info(self.h, buf, 64))
+        return buf.value.decode()
 
     def comm_info(self):
         """(kind, rank, world) of the attached communicator: kind "none" / "rccl" / "host"; for RCCL
