@@ -13,6 +13,7 @@
  *   ppo_get_action_and_value         Agent::get_action_and_value (ppo:145-157, ac:212-249) + Normal/Beta
  *                                    (include/rl_utils.h:20-132)
  *   ppo_get_value                    Agent::get_value (ppo:140-143, ac:188-192)
+ *   ppo_values                       Agent::get_value over many stored rows, throughput-first
  *   ppo_rollout_act                  one rollout step's agent half: obs/dones/actions/logprobs/values stores
  *                                    (ppo:387-400, ac:649-660) for envs [env_begin, env_end)
  *   ppo_rollout_reward               rewards[step] store (ppo:406, ac:668)
@@ -197,6 +198,14 @@ int ppo_get_action_and_value(ppo_t* ctx, int n, const float* x_dev, int sample_t
                              float* action_dev, float* logprob_dev, float* entropy_dev, float* value_dev,
                              void* stream);
 int ppo_get_value(ppo_t* ctx, int n, const float* x_dev, float* value_dev, void* stream);
+/* The batched critic: values_dev[i] = critic(obs_dev[i]) for any n > 0 contiguous rows of [n][obs_dim]
+ * observations, by the kernel that the persistent rollout's value pass uses (throughput-first: the
+ * critic's weights stay in registers across rows; k_values / k_values4, k_vbx on a values_mfma=bx6
+ * context, k_values_w for the AC agent at hidden 256 with obs_dim padded to 384, any act_dim), and by
+ * ppo_get_value's kernel for a shape that has none. Where both kernels are fp32 (every one but k_vbx) the
+ * values are bitwise ppo_get_value's. Works on an update=off context. Refuses n <= 0 and NULL pointers
+ * with a message. */
+int ppo_values(ppo_t* ctx, long n, const float* obs_dev, float* values_dev, void* stream);
 
 /* rollout step `step` for envs [env_begin, env_end): stores obs/dones, samples actions with the
  * Philox key (seed, rank, env, iteration*T + step), writes actions into storage and (if non-NULL)

@@ -455,7 +455,8 @@ extern "C" int ppo_rollout_reward(ppo_t* c, int step, int e0, int e1, const floa
 
 static int gae_launch(ppo_t* c, const float* next_value, const float* next_done, int nsteps, hipStream_t s);
 
-// the critic over n contiguous observation rows (k_vbx with the critic's W2 pieces, else k_values)
+// the critic over n contiguous observation rows (k_vbx with the critic's W2 pieces, else launch_values:
+// k_values / k_values4, k_values_w at OP = 384 of the AC agent)
 int run_values(ppo_t* c, const float* obs, float* values, long n, hipStream_t s) {
   ValuesArgs v;
   v.P = c->P;
@@ -468,6 +469,18 @@ int run_values(ppo_t* c, const float* obs, float* values, long n, hipStream_t s)
   ProfScope ps(c, PK_VALUES, s);
   if (v.WBX) return launch_vbx(v, s) == 0 ? 0 : -1;
   return launch_values(v, s);
+}
+extern "C" int ppo_values(ppo_t* c, long n, const float* obs, float* values, void* stream) {
+  if (!c || !obs || !values) return fail("ppo_values: null argument");
+  if (n <= 0) return fail("ppo_values: n must be positive, got " + std::to_string(n));
+  // no batched critic kernel for the shape (the AC agent above 8 actions below OP = 384): k_act3's critic
+  if (rollout_supported(c->K) != 0 && values_w_supported(c->K) != 0) {
+    if (n > 0x7fffffffL) return fail("ppo_values: more than 2^31 - 1 rows at a shape without a batched critic kernel");
+    return ppo_get_value(c, (int)n, obs, values, stream);
+  }
+  if (run_values(c, obs, values, n, S(c, stream)) != 0) return fail("ppo_values: values kernel launch failed");
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 // the deferred critic pass of per-step rollouts (ppo_rollout_act with values_bx): values[t] for every
 // step acted so far, over the stored observations

@@ -108,6 +108,16 @@ extern "C" int psyn_step(psyn_t* env, int e0, int e1, const float* act, float lo
   return 0;
 }
 
+// k_rollout_w's value pass over the n = T E stored rows: k_values_w from this many rows on, k_act3's critic
+// workgroups (ppo_get_value) below; the values are the same bits either way. Measured on an MI355X, HIP
+// events per launch, medians of three alternating repetitions (profiles/values_wide/values_wide_timing.txt),
+// k_values_w / k_act3: n = 2 048: 31.4 / 21.6 us, 4 096: 32.6 / 22.4 us, 8 192: 33.9 / 40.4 us, 16 384: 60.8 /
+// 76.6 us, 32 768: 110.8 / 144.3 us, 524 288: 1 539 / 2 156 us. Up to 4 096 rows k_act3's 16-row workgroups
+// are one round of the 256 CUs, and k_values_w's 32-row passes leave CUs idle after a longer prologue (W2
+// into registers); from 8 192 rows on every repetition of k_values_w beat every one of k_act3. Between the
+// two sizes nothing was measured, so the threshold is the smallest size at which it won.
+constexpr long kValuesWMinRows = 8192;
+
 // the persistent rollout's arguments that come from the context; the caller adds the env and its state
 static RolloutArgs base_rollout(ppo_t* c) {
   RolloutArgs r;
@@ -163,10 +173,14 @@ extern "C" int ppo_rollout_synth(ppo_t* c, psyn_t* env, float* next_obs, float* 
       launch_beta_logp(r.s_beta, c->buf[PPO_BUF_LOGPROBS], n, c->K.A, c->stream);
     }
     c->values_pending.store(0);  // every stored row's value comes from this pass
-    // k_values (run_values) serves rollout_supported's set, which ends at OP = 112: at this width the critic
-    // of the stored rows is k_act3's critic workgroups, one launch over all T E rows. It is the kernel the
-    // per-step path's values come from, and a row's value does not depend on the rows beside it.
-    if (int rc = ppo_get_value(c, (int)n, c->buf[PPO_BUF_OBS], c->buf[PPO_BUF_VALUES], c->stream)) return rc;
+    // the critic of the stored rows: k_values_w (run_values), bitwise k_act3's critic workgroups, which the
+    // per-step path's values come from; a row's value does not depend on the rows beside it
+    if (n >= kValuesWMinRows) {
+      if (run_values(c, c->buf[PPO_BUF_OBS], c->buf[PPO_BUF_VALUES], n, c->stream) != 0)
+        return fail("ppo_rollout_synth: values kernel launch failed");
+    } else if (int rc = ppo_get_value(c, (int)n, c->buf[PPO_BUF_OBS], c->buf[PPO_BUF_VALUES], c->stream)) {
+      return rc;
+    }
     HIP_TRY(hipGetLastError());
     c->rollout_path = 4;
     return 0;

@@ -114,7 +114,7 @@ static void name_kernels(const PackedLayout& K, KernelPlan* p) {
                                                     : "k_dwf_dma/f32")
                : (p->dw_dma && H == 256 && OP == 112) ? "k_dw_dma" + bxs
                                                       : "k_dw";
-  p->values_name = rollout_supported(K) != 0 ? "k_act" : p->values_bx ? "k_vbx/bx6"
+  p->values_name = values_w_supported(K) == 0 ? "k_values_w/f32" : rollout_supported(K) != 0 ? "k_act" : p->values_bx ? "k_vbx/bx6"
                    : K.kind == PPO_NET_TANH_NORMAL ? "k_values4/f32" : "k_values/f32";
   // the create option, not the per-update decision (a communicator turns the fold off)
   p->norm_name = p->gn_fold && !p->gradstep ? "k_colsum" : p->gradstep ? "k_gradstep" : "k_gradnorm";

@@ -347,6 +347,10 @@ int rollout_w_supported(const PackedLayout& K);
 // whose bytes do not fit the kernel's 32-bit store offsets
 int launch_rollout_w(const RolloutArgs& a, hipStream_t s);
 int launch_values(const ValuesArgs& a, hipStream_t s);
+// k_values_w (ppo_values_wide.hip), the AC agent's batched critic at Humanoid width: LayerNorm-Beta, H = 256,
+// OP = 384, any A (the critic has one head); launch_values dispatches the shape to it
+int values_w_supported(const PackedLayout& K);
+int launch_values_w(const ValuesArgs& a, hipStream_t s);  // -1 when the shape is not covered, -2 the LDS attribute
 int launch_beta_logp(const float* s_beta, float* logp, long n, int A, hipStream_t s);
 
 // sets the thread-local ppo_last_error() message and returns code (ppo_capi.hip)

@@ -18,6 +18,7 @@
 //    split over wave halves, every device env kind; not bitwise the others (DESIGN §3b').
 //  * k_rollout_w (ppo_rollout_wide.hip): k_rollout's contract at Humanoid width (OP = 384, 17 <= A <= 24),
 //    W1 streamed from L2 every step, the rollout stores through buffer resources.
+//  * k_values_w (ppo_values_wide.hip): k_values's contract at that width, W1 streamed once per 32 rows.
 // They use the building blocks of k_act3 (ppo_act_common.hpp) in the same order: every action,
 // log-prob, value, reward and observation is bitwise the one the per-step path produces
 // (tests/test_gpu_rollout.py).
@@ -1183,6 +1184,7 @@ static int launch_values_t(const ValuesArgs& a, hipStream_t s) {
 }
 
 int launch_values(const ValuesArgs& a, hipStream_t s) {
+  if (values_w_supported(a.K) == 0) return launch_values_w(a, s);  // the AC agent at nto == 24: k_values_w
   if (rollout_supported(a.K) != 0) return -1;
   if (a.K.kind == PPO_NET_TANH_NORMAL) {
     switch (a.K.OP / 16) {

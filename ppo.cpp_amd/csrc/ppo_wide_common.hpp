@@ -1,7 +1,7 @@
 // ppo_wide_common.hpp — what the persistent kernels of the AC agent at Humanoid width share: k_eval_w
-// (ppo_eval_wide.hip) and k_rollout_w (ppo_rollout_wide.hip). The LDS carve with one region for XS, HB, HP
-// and ITM in turn (WideGeo), and layer 1 with W1 streamed from L2 through a ring of k-blocks (ring_fill,
-// layer1_ring). DESIGN 3d, "k_eval_w".
+// (ppo_eval_wide.hip), k_rollout_w (ppo_rollout_wide.hip) and k_values_w (ppo_values_wide.hip). The LDS
+// carve of the first two with one region for XS, HB, HP and ITM in turn (WideGeo), and layer 1 with W1
+// streamed from L2 through a ring of k-blocks (ring_fill, layer1_ring). DESIGN 3d, "k_eval_w".
 #pragma once
 
 #include "ppo_rollout_common.hpp"
@@ -38,13 +38,15 @@ struct WideGeo {
   static_assert(total * sizeof(float) <= 160 * 1024, "WideGeo: the LDS carve exceeds a CU's 160 KB");
 };
 
-// Layer 1 for this wave's 2 output tiles of the 16 rows in XS, the A operands streamed through the ring
-// w, whose slot p the caller has filled with k-block p (ring_fill, issued before the rows are
-// normalised). This is act_layer<NKB, D, 1> (ppo_act_common.hpp) said a second time for two things it
-// does not do: the ring's first fill is the caller's, one phase earlier, and the next k-block's B
-// operand is read from LDS under this k-block's MFMAs instead of in front of its own. Each accumulator
-// sees k-blocks 0 .. NKB - 1 ascending and .x .y .z .w within a block, as in act_layer /
-// act_layer_regs, so the results are bitwise theirs.
+// Layer 1 for this wave's 2 output tiles of the 16 RT rows in XS (row tile rt starts LDT floats after
+// row tile rt - 1; RT = 1: k_eval_w / k_rollout_w, RT = 2: k_values_w), the A operands streamed through
+// the ring w, whose slot p the caller has filled with k-block p (ring_fill, issued before the rows are
+// normalised). One ring load of a k-block feeds the MFMAs of all RT row tiles. This is
+// act_layer<NKB, D, RT> (ppo_act_common.hpp) said a second time for two things it does not do: the
+// ring's first fill is the caller's, one phase earlier, and the next k-block's B operands are read from
+// LDS under this k-block's MFMAs instead of in front of their own. Each accumulator sees k-blocks
+// 0 .. NKB - 1 ascending and .x .y .z .w within a block, as in act_layer / act_layer_regs, so the
+// results are bitwise theirs.
 template <int NKB, int D>
 PPO_DEV void ring_fill(f4 (&w)[D][2], PBuf wb, int wlane) {
 #pragma unroll
@@ -52,23 +54,31 @@ PPO_DEV void ring_fill(f4 (&w)[D][2], PBuf wb, int wlane) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) w[p][u] = pld4(wb, wlane, 256 * (NKB * u + p));
 }
-template <int NKB, int D>
-PPO_DEV void layer1_ring(f4 (&acc)[2][1], f4 (&w)[D][2], PBuf wb, int wlane, const float* xin) {
+template <int NKB, int D, int LDT = 0, int RT>
+PPO_DEV void layer1_ring(f4 (&acc)[2][RT], f4 (&w)[D][2], PBuf wb, int wlane, const float* xin) {
   static_assert(D <= NKB, "ring deeper than the layer");
-  f4 b = *reinterpret_cast<const f4*>(xin);
+  static_assert(RT == 1 || LDT > 0, "more than one row tile needs the tiles' stride");
+  f4 b[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) b[rt] = *reinterpret_cast<const f4*>(xin + LDT * rt);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int t = 0; t < NKB; ++t) {
-    const f4 bn = *reinterpret_cast<const f4*>(xin + 16 * (t + 1 < NKB ? t + 1 : t));
+    f4 bn[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) bn[rt] = *reinterpret_cast<const f4*>(xin + LDT * rt + 16 * (t + 1 < NKB ? t + 1 : t));
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int u = 0; u < 2; ++u) acc[u][0] = mfma16(w[t % D][u][c], b[c], acc[u][0]);
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) acc[u][rt] = mfma16(w[t % D][u][c], b[rt][c], acc[u][rt]);
     if (t + D < NKB) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) w[t % D][u] = pld4(wb, wlane, 256 * (NKB * u + t + D));
     }
-    b = bn;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) b[rt] = bn[rt];
     // keeps the refill where it is written (the scheduler otherwise sinks it towards its use)
     __builtin_amdgcn_sched_barrier(0);
   }

@@ -181,6 +181,7 @@ SYMBOLS = [
     ("ppo_load_adam", _I, [_VP, _FP, _FP, _L, _L]),
     ("ppo_get_action_and_value", _I, [_VP, _I, _FP, _I, _FP, _L, _L, _FP, _FP, _FP, _FP, _VP]),
     ("ppo_get_value", _I, [_VP, _I, _FP, _FP, _VP]),
+    ("ppo_values", _I, [_VP, _L, _FP, _FP, _VP]),
     ("ppo_rollout_act", _I, [_VP, _I, _I, _I, _FP, _FP, _FP, _VP]),
     ("ppo_rollout_values", _I, [_VP, _VP]),
     ("ppo_rollout_reward", _I, [_VP, _I, _I, _I, _FP, _VP]),
@@ -698,6 +699,14 @@ class Agent:
         n = x.shape[0]
         val = DeviceArray(n)
         check(lib().ppo_get_value(self.h, n, x.ptr, val.ptr, None))
+        return val
+
+    def values(self, x: DeviceArray):
+        """The batched critic over the rows of x ([n, obs_dim]) by the kernel of the persistent rollout's value
+        pass (ppo_values): k_values / k_values4 / k_vbx, k_values_w at Humanoid width."""
+        n = x.shape[0]
+        val = DeviceArray(n)
+        check(lib().ppo_values(self.h, n, x.ptr, val.ptr, None))
         return val
 
     def buffer(self, which, shape):
