@@ -75,6 +75,47 @@ def grid_loads(A):
     return out
 
 
+def tile_edge_columns(A):
+    """The action columns either side of a 16-row head-tile boundary of the 2 A head rows (alpha rows 0 .. A - 1,
+    then beta rows A .. 2 A - 1: act_head_row, ppo_act_common.hpp), with the first and the last column. The
+    alpha rows cross at column 16; beta column c is head row A + c, which crosses at c = 32 - A (A + c = 16
+    has no c >= 0 from A = 17 on)."""
+    assert 17 <= A <= 24
+    return sorted({0, 15, 16, A - 1, 31 - A, 32 - A})
+
+
+def tile_edge_loads(A):
+    """grid_loads(A), then rotated copies of its first group (np.roll of the pair list: (1, 1) sits at 0 and
+    (1000, 1000) at 13) until both the alpha and the beta of every tile-edge column have been exactly 1 in
+    some load and 1000 in some load."""
+    loads = grid_loads(A)
+    first = loads[0]
+    assert first[0] == (1.0, 1.0) and first[13] == (1000.0, 1000.0)
+    for c in tile_edge_columns(A):
+        for target, at in ((1.0, 0), (1000.0, 13)):
+            if not all(any(l[c][h] == target for l in loads) for h in (0, 1)):
+                loads.append([first[i] for i in np.roll(np.arange(A), c - at)])
+    return loads
+
+
+# the three parameter loads of the collection tests: six (alpha, beta) pairs each
+COLLECT_LOADS = {
+    "near_one": [(1.0, 1.0), (Bias(-15.0), Bias(-15.0)), (1.05, 1.05), (1.5, 1.0), (1.0, 2.0), (1.05, 1.0)],
+    "thresholds": [(3.0, 3.0), (5.9999995, 5.9999995), (6.0, 6.0), (9.5, 9.5), (10.0, 1.0), (21.0, 2.1)],
+    "trained": [(100.0, 100.0), (1000.0, 1000.0), (1000.0, 1.0), (1.0, 1000.0), (100.0, 10.0), (1000.0, 100.0)],
+}
+# column c of the wide load takes pair (c + offset) % 6. The offsets put (1000, 1000) | (1000, 1) at A = 17
+# and (1000, 1) | (1, 1000) at A = 20 on columns 15 | 16 of "trained" (the alpha rows' tile boundary), and
+# 1 + 3e-7 | 1.05 and 1.05 | (1.5, 1) on those of "near_one".
+WIDE_OFFSET = {17: 4, 20: 5}
+
+
+def wide_collect_load(name, A):
+    """The family's six pairs cycled over A columns from the shape's offset."""
+    pairs = COLLECT_LOADS[name]
+    return [pairs[(c + WIDE_OFFSET[A]) % len(pairs)] for c in range(A)]
+
+
 def _softplus64(b):
     b = np.asarray(b, np.float64)
     return np.where(b > 20.0, b, np.log1p(np.exp(np.minimum(b, 20.0))))

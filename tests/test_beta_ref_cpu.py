@@ -158,6 +158,74 @@ def test_oracle_sampler_passes_the_moment_bounds():
     print("oracle sampler, largest |deviation| / (5 sd) of mean, variance, third moment:", worst.round(3))
 
 
+@pytest.mark.parametrize("A", [17, 20])
+@pytest.mark.parametrize("name", list(B.COLLECT_LOADS))
+def test_oracle_sampler_passes_the_moment_bounds_at_the_wide_loads(name, A):
+    """The precondition of test_gpu_beta_range.py::test_collection_paths_wide: at its concentrations
+    (wide_collect_load), its 37 envs x 32 steps and its seed (1, iteration 0), the oracle's sampler passes the
+    5-sigma moment bounds in every action dimension, so a correct kernel sampler can. Per shape "trained" holds
+    a 1000 and "near_one" a concentration of at most 1.05 on both columns 15 and 16."""
+    al, be = (B.conc_of_bias(b) for b in _biases(B.wide_collect_load(name, A)))
+    for c in (15, 16):
+        assert name != "trained" or max(al[c], be[c]) == 1000.0
+        assert name != "near_one" or min(al[c], be[c]) <= np.float32(1.05)
+    worst = np.zeros(3)
+    for a in range(A):
+        s = B.oracle_samples(al[a], be[a], a, 37, 32, seed=1)
+        assert s.min() >= B.FLT_MIN and s.max() <= B.S_MAX
+        r = np.array(B.moment_check(s.ravel(), al[a], be[a]))
+        assert (r < 1).all(), (a, float(al[a]), float(be[a]), r)
+        worst = np.maximum(worst, r)
+    print(f"oracle sampler at {name}, A = {A}: largest |deviation| / (5 sd)", worst.round(3))
+
+
+@pytest.mark.parametrize("A", [17, 20])
+def test_tile_edge_loads_put_the_grids_edges_on_the_head_tile_boundaries(A):
+    """The 2 A head rows are alpha 0 .. A - 1, then beta 0 .. A - 1, in tiles of 16: the alpha rows cross a
+    tile at column 16, the beta rows at column 32 - A. tile_edge_loads keeps every load of grid_loads, adds
+    only rotations of its first group, and over its loads the alpha and the beta of the columns either side
+    of both boundaries, of column 0 and of column A - 1 are exactly 1 somewhere and 1000 somewhere."""
+    cols = B.tile_edge_columns(A)
+    assert {0, 15, 16, A - 1, 31 - A, 32 - A} == set(cols) and (A + 31 - A) // 16 != (A + 32 - A) // 16
+    base, loads = B.grid_loads(A), B.tile_edge_loads(A)
+    assert len(base) == 3 and loads[:3] == base
+    for extra in loads[3:]:
+        assert any(extra == [base[0][i] for i in np.roll(np.arange(A), k)] for k in range(A))
+    conc = [tuple(B.conc_of_bias(b) for b in _biases(load)) for load in loads]
+    for c in cols:
+        for h in (0, 1):
+            assert {1.0, 1000.0} <= {float(ab[h][c]) for ab in conc}, (c, h)
+
+
+@pytest.mark.parametrize("A", [17, 20])
+def test_reference_fp32_row_sums_stay_within_the_bound_at_17_to_20_addends(A):
+    """K_REF and FLOOR_ITEM are measured per item (test_reference_fp32_arithmetic_measures_k_ref), and before
+    this test the row bound was only ever compared with an fp32 sum of at most 8 items on the GPU (17 in the
+    oracle, which accumulates a row in double). Here the reference's own fp32 formula (beta_torch_fp32) is
+    summed over the row in fp32, as the reference's sum(-1) does, at A = 17 and 20 over the loads of
+    test_forward_given_mean_roach's wide shapes (tile_edge_loads and the far point), at every given-action
+    case and at the mean and roach actions: log-prob and entropy within row_bounds of beta_fp64, at factor 1
+    (the reference's arithmetic; a kernel is allowed twice that), non-finite exactly where the restatement is.
+    A correct fp32 copy can therefore pass the GPU checks at these widths."""
+    worst = {"lp": 0.0, "ent": 0.0}
+    for load in B.tile_edge_loads(A) + [[B.FAR] * A]:
+        al, be = (B.conc_of_bias(b) for b in _biases(load))
+        given, names = B.given_actions(al, be, len(B.GIVEN))
+        cases = [("given", B.scale_action(given)), ("mean", B.mean01(al, be)[None, :]), ("roach", B.roach01(al, be)[None, :])]
+        for mode, s in cases:
+            ala, bea = np.tile(al, (s.shape[0], 1)), np.tile(be, (s.shape[0], 1))
+            ref, f32 = B.beta_fp64(ala, bea, s), B.beta_torch_fp32(ala, bea, s)
+            bd = B.row_bounds(ref, factor=1.0)
+            for q in ("lp", "ent"):
+                r, f = ref[q].numpy().sum(-1), f32[q].sum(-1).double().numpy()
+                assert same_nonfinite(f, r), (mode, q, load, f, r)
+                ok = np.isfinite(r)
+                ratio = np.abs(f[ok] - r[ok]) / bd[q][ok]
+                worst[q] = max(worst[q], ratio.max())
+                assert (ratio <= 1).all(), (mode, q, load, names, ratio)
+    print(f"reference fp32 row sums at A = {A}, largest error / bound (factor 1):", worst)
+
+
 def test_central_moments_are_exact():
     """Beta(2, 3): mean 2/5, variance 1/25, third central moment 2/875 (closed forms)."""
     mu, m = B.beta_central_moments(2.0, 3.0)

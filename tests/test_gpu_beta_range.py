@@ -5,11 +5,14 @@ thousand of a trained policy; at given actions on the clamps (lo, hi, beyond bot
 sample 1 - 2^-24). The bound scales with the addends (beta_ref's module docstring); its constants are measured
 on the reference's fp32 arithmetic in tests/test_beta_ref_cpu.py.
 
-Copies reached: k_act3 with one and two input blocks, k_act2 (hidden 64), k_carla_tail,
-k_carla_head; k_rollout + k_beta_logp, k_rollout_v + k_beta_logp, the per-step ppo_rollout_act, k_eval;
+Copies reached: k_act3 with one and two input blocks, its three-head-tile forms
+(2 A = 34 to 40 head rows: <24, 3> at O = 376 and 384, <2, 3> at O = 17; acting-only contexts, update=off),
+k_act2 (hidden 64), k_carla_tail, k_carla_head; k_rollout + k_beta_logp, k_rollout_v + k_beta_logp,
+k_rollout_w + k_beta_logp (A = 17 and 20), the per-step ppo_rollout_act at both widths, k_eval, k_eval_w;
 k_upd's 8-lane group (A = 3, 6, 8) as bx6 / fp32 16x16x4 / k_upd32 / its mixed form, k_fwdbwd at hidden 256
-and 64, k_carla_head_bwd. Not reached through the C-ABI: k_upd's LDS item path for A > 8 (below), k_rollout
-with log-probs in the loop (ppo_rollout_synth always defers them for this agent).
+and 64, k_carla_head_bwd. Not reached through the C-ABI: k_upd's LDS item path for A > 8 (a context that
+updates is refused from A = 13 on, below); as before, k_rollout with log-probs in the loop
+(ppo_rollout_synth always defers them for this agent).
 
 Behaviour the reference shares and the tests expect: log-prob -inf at action = hi with beta > 1 (s = 1,
 log 0), NaN at an action above hi (scale_action's upper clamp is 1 + 1e-7f = 1 + 2^-23, so 1 - s < 0), and at
@@ -24,10 +27,15 @@ import beta_ref as B  # noqa: E402
 import oracle_lib as Orc  # noqa: E402
 from ppo_amd import DeviceArray  # noqa: E402
 from test_gpu_parity import fill_storage, rel  # noqa: E402
+from test_gpu_rollout_wide import Side  # noqa: E402
 
 # (O, A, H): k_act3 two input blocks + k_upd 8-lane group with two idle lanes; one input block; the full
-# group; hidden 64: k_act2 and k_fwdbwd. No A > 8 at hidden 256 (test_a_above_8_is_out_of_reach_at_hidden_256)
+# group; hidden 64: k_act2 and k_fwdbwd. A context that updates takes no A > 12 at hidden 256
+# (test_a_above_8_is_out_of_reach_at_hidden_256); the update tests use these
 SHAPES = [(17, 6, 256), (11, 3, 256), (17, 8, 256), (17, 6, 64)]
+# acting-only contexts (update=off), forward only: k_act3<24, 3> at the smallest A with a third head tile (544
+# Beta items on 512 threads) and at O = OP with the widest A a context takes (640 items); k_act3<2, 3>
+WIDE_SHAPES = [(376, 17, 256), (384, 20, 256), (17, 17, 256)]
 ROWS = (1, 3, 70)
 E_UPD, T_UPD = 37, 3          # M = 111: a ragged last tile, whose padding rows take the kernels' !valid path
 CLIP = 0.2
@@ -90,31 +98,53 @@ def check_forward(copy, mode, act_dev, lp, ent, al, be, act_given, names, load):
 # ------------------------------------------------------------------------------------------------
 # (a) forward: every act copy
 # ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", params=SHAPES, ids=lambda s: "O%d_A%d_H%d" % s)
+@pytest.fixture(scope="module", params=SHAPES + WIDE_SHAPES, ids=lambda s: "O%d_A%d_H%d" % s)
 def act_agent(request):
     O_, A, H = request.param
-    ag = make_agent(O_, A, H)
+    ag = make_agent(O_, A, H, options="update=off" if request.param in WIDE_SHAPES else None)
     yield ag, Orc.layout_init(1, O_, A, H)
     ag.close()
+
+
+def act_copy(L):
+    """the act kernel of a layout as launch_act3 picks it: input blocks of 16 (OP), head tiles of 16 rows"""
+    if L.H == 64:
+        return "k_act2"
+    nht = (2 * L.A + 15) // 16
+    return "k_act3/OP%d" % ((L.O + 15) // 16 * 16) + ("/NHT%d" % nht if nht > 1 else "")
 
 
 @pytest.mark.parametrize("n", ROWS)
 def test_forward_given_mean_roach(act_agent, n):
     """ppo_get_action_and_value in PPO_GIVEN / PPO_MEAN / PPO_ROACH over every grid load and the far point
     (1e4, 1e4): log-prob and entropy per row within the bound, the returned actions within the existing
-    action bars, -inf (not NaN) at action = hi with beta > 1, NaN exactly where the reference has it."""
+    action bars, -inf (not NaN) at action = hi with beta > 1, NaN exactly where the reference has it.
+
+    The wide shapes (three head tiles; a context that updates is still refused there) run tile_edge_loads:
+    the grid's loads and rotated copies, so that the alpha and the beta of every action column next to a
+    head-tile boundary (beta_ref.tile_edge_columns) is exactly 1 in some load and 1000 in some load."""
     ag, L = act_agent
-    copy = "k_act2" if L.H == 64 else "k_act3/OP%d" % (16 if L.O <= 16 else 32)
+    wide = (L.O, L.A, L.H) in WIDE_SHAPES
+    copy = act_copy(L)
     rng = np.random.default_rng(100 * L.O + L.A + L.H + n)
     x = DeviceArray.from_numpy(rng.standard_normal((n, L.O)).astype(np.float32))
-    for load in B.grid_loads(L.A) + [[B.FAR] * L.A]:
+    if wide:
+        with pytest.raises(ppo_amd.PPOError):
+            make_agent(L.O, L.A, L.H)
+    seen = []
+    for load in (B.tile_edge_loads(L.A) if wide else B.grid_loads(L.A)) + [[B.FAR] * L.A]:
         p, al, be = B.head_params(L, rng, [t[0] for t in load], [t[1] for t in load])
+        seen.append((al, be))
         ag.load_params(p)
         given, names = B.given_actions(al, be, n)
         for mode, m in MODES.items():
             a = DeviceArray.from_numpy(given) if mode == "given" else None
             act, lp, ent, _ = ag.get_action_and_value(x, m, a)
             check_forward(copy, mode, act.numpy(), lp.numpy(), ent.numpy(), al, be, given, names, load)
+    if wide:
+        for c in B.tile_edge_columns(L.A):
+            for h in (0, 1):
+                assert {1.0, 1000.0} <= {float(ab[h][c]) for ab in seen}, (c, h)
 
 
 @pytest.mark.parametrize("tail", ["fused", "layers"])
@@ -164,11 +194,7 @@ def carla_head_params(L, base, load):
 # ------------------------------------------------------------------------------------------------
 # (b) collection: every path
 # ------------------------------------------------------------------------------------------------
-COLLECT_LOADS = {
-    "near_one": [(1.0, 1.0), (B.Bias(-15.0), B.Bias(-15.0)), (1.05, 1.05), (1.5, 1.0), (1.0, 2.0), (1.05, 1.0)],
-    "thresholds": [(3.0, 3.0), (5.9999995, 5.9999995), (6.0, 6.0), (9.5, 9.5), (10.0, 1.0), (21.0, 2.1)],
-    "trained": [(100.0, 100.0), (1000.0, 1000.0), (1000.0, 1.0), (1.0, 1000.0), (100.0, 10.0), (1000.0, 100.0)],
-}
+COLLECT_LOADS = B.COLLECT_LOADS   # near_one, thresholds, trained: six (alpha, beta) pairs each
 E_COL, T_COL = 37, 32
 PATHS = {"per_step": "rollout=per_step", "k_rollout": "rollout_kernel=mfma", "k_rollout_v": "rollout_kernel=valu"}
 
@@ -236,6 +262,72 @@ def test_eval_sampled_action(name):
         assert np.isfinite(fast[0]).all()
         np.testing.assert_array_equal(fast[0].view(np.uint32), slow[0].view(np.uint32))
         np.testing.assert_array_equal(fast[1], slow[1])
+    finally:
+        ag.close(); env.close()
+
+
+@pytest.mark.parametrize("shape", [(376, 17), (384, 20)], ids=lambda s: "O%d_A%d" % s)
+@pytest.mark.parametrize("name", list(COLLECT_LOADS))
+def test_collection_paths_wide(name, shape):
+    """test_collection_paths at Humanoid width: one rollout of 37 envs x 32 steps (three workgroups, the last
+    of 5 rows) on two acting-only contexts, k_rollout_w (544 / 640 Beta items on 512 threads: a thread's
+    second item has its own Philox draws and rejection loop) and the per-step ppo_rollout_act, both with the
+    deferred k_beta_logp. The family's six pairs are cycled over the A columns (beta_ref.wide_collect_load);
+    tests/test_beta_ref_cpu.py shows the oracle's sampler passing the same moment bounds at the same
+    concentrations, counters and seed."""
+    O_, A = shape
+    load = B.wide_collect_load(name, A)
+    L = Orc.layout_init(1, O_, A, 256)
+    p, al, be = B.head_params(L, np.random.default_rng(5), [t[0] for t in load], [t[1] for t in load])
+    sides = [Side(O_, A, E_COL, T_COL, o) for o in ("update=off", "update=off,rollout=per_step")]
+    try:
+        for s_ in sides:
+            s_.ag.load_params(p)
+        (fast, finfo), (slow, sinfo) = [s_.rollout(0) for s_ in sides]
+        assert finfo == "rollout=k_rollout_w" and sinfo == "rollout=per_step"
+        act, lp = slow["actions"], slow["logprobs"]
+        np.testing.assert_array_equal(fast["actions"].view(np.uint32), act.view(np.uint32), err_msg="actions")
+        np.testing.assert_array_equal(fast["logprobs"].view(np.uint32), lp.view(np.uint32), err_msg="logprobs")
+        assert np.isfinite(lp).all()
+        s = B.scale_action(act)
+        assert s.max() <= B.S_MAX and (act >= B.LO).all() and (act < B.HI).all()
+        a2 = act.reshape(-1, A)
+        ref = B.beta_fp64(*expand(al, be, a2.shape[0]), s.reshape(-1, A))
+        bd = B.row_bounds(ref, stored_action=a2)
+        r = np.abs(lp.reshape(-1) - ref["lp"].numpy().sum(-1)) / bd["lp"]
+        note("collection_w/A%d/%s" % (A, name), "logp", r.max())
+        assert (r <= 1).all(), r.max()
+        for a in range(A):
+            m = np.array(B.moment_check(s[:, :, a].ravel(), al[a], be[a]))
+            note("sampler_w/A%d/%s" % (A, name), "moments", m.max())
+            assert (m < 1).all(), (a, load[a], m)
+    finally:
+        for s_ in sides:
+            s_.close()
+
+
+@pytest.mark.parametrize("name", list(COLLECT_LOADS))
+def test_eval_sampled_action_wide(name):
+    """k_eval_w at O = 376, A = 17 at each parameter load: two evaluation episodes on two of four envs, with
+    the sampled, the mean and the roach action, give bitwise the returns, lengths and step count of the
+    per-step path (k_act3<24, 3> + the env step), finite."""
+    O_, A = 376, 17
+    load = B.wide_collect_load(name, A)
+    L = Orc.layout_init(1, O_, A, 256)
+    p, _, _ = B.head_params(L, np.random.default_rng(5), [t[0] for t in load], [t[1] for t in load])
+    ag = make_agent(O_, A, 256, options="update=off")
+    env = ppo_amd.SynthEnv(4, O_, A)
+    try:
+        ag.load_params(p)
+        for mode in (ppo_amd.PPO_SAMPLE, ppo_amd.PPO_MEAN, ppo_amd.PPO_ROACH):
+            fast = ag.evaluate(env, 2, mode, eval_seed=3, num_eval_envs=2, persistent=True)
+            assert ag.eval_info() == "eval=k_eval_w"
+            slow = ag.evaluate(env, 2, mode, eval_seed=3, num_eval_envs=2, per_step=True)
+            assert ag.eval_info() == "eval=per_step"
+            assert fast[0].size >= 2 and np.isfinite(fast[0]).all()
+            np.testing.assert_array_equal(fast[0].view(np.uint32), slow[0].view(np.uint32))
+            np.testing.assert_array_equal(fast[1], slow[1])
+            assert fast[2] == slow[2]
     finally:
         ag.close(); env.close()
 
@@ -315,11 +407,12 @@ def test_update_head_gradients(shape, opts, kernel, setting):
 
 
 def test_a_above_8_is_out_of_reach_at_hidden_256():
-    """k_upd's second Beta branch (A > 8: items in LDS) and k_act3's three-head-tile form exist for A in 17..20
-    only, and ppo_create refuses those shapes for the LayerNorm-Beta agent: every context sizes k_fwdbwd's LDS
-    for its 2 A head rows, which passes 160 KiB from A = 13 on. The refusal must leave no HIP error behind
-    for the next call to find (it did: the following ppo_load_params of another context failed with
-    "invalid argument")."""
+    """k_upd's second Beta branch (A > 8: items in LDS) exists for A in 17..20 only, and those shapes are out
+    of reach for a context that updates: ppo_create refuses them for the LayerNorm-Beta agent, because such
+    a context sizes k_fwdbwd's LDS for its 2 A head rows, which passes 160 KiB from A = 13 on. With the create
+    option update=off the shapes are reachable as acting-only contexts, and k_act3's three-head-tile forms,
+    k_rollout_w and k_eval_w are tested above. The refusal must leave no HIP error behind for the next call
+    to find (it did: the following ppo_load_params of another context failed with "invalid argument")."""
     ag = make_agent(17, 6, 64)
     try:
         with pytest.raises(ppo_amd.PPOError, match="cannot set LDS size"):

@@ -85,11 +85,22 @@ def test_act_given_action_vs_golden(case, kind):
         np.testing.assert_allclose(am.numpy(), d["mean"], rtol=1e-5, atol=2e-6)
 
 
-@pytest.mark.parametrize("kind,O_,A,H,n", [(1, 17, 6, 256, 1000), (0, 17, 6, 64, 777), (0, 376, 17, 64, 300),
-                                           (1, 105, 8, 256, 200)])
-def test_act_vs_oracle_given_mean_sample(kind, O_, A, H, n):
+# The update=off cases: the LayerNorm-Beta agent at hidden 256 with 2 A = 34 to 40 head rows, live head weights
+# in all three head tiles of k_act3 (acting-only contexts; one that updates is refused from A = 13 on): <24, 3>
+# at O = 376, at O = 373 (a ragged last k-block of layer 1) and at O = OP = 384 with the widest A, <2, 3> at
+# O = 17. n A >= 3 400 leaves the sampled-action cap room for three accept flips (the cases before: at least
+# one, at 1 600 items); every n ends on a ragged 16-row workgroup.
+ACT_ORACLE_CASES = [(1, 17, 6, 256, 1000, None), (0, 17, 6, 64, 777, None), (0, 376, 17, 64, 300, None),
+                    (1, 105, 8, 256, 200, None), (1, 376, 17, 256, 200, "update=off"), (1, 373, 17, 256, 200, "update=off"),
+                    (1, 384, 20, 256, 170, "update=off"), (1, 17, 17, 256, 200, "update=off")]
+
+
+@pytest.mark.parametrize("kind,O_,A,H,n,options", ACT_ORACLE_CASES,
+                         ids=["-".join(str(v) for v in c[:5]) + ("-" + c[5].replace("=", "_") if c[5] else "")
+                              for c in ACT_ORACLE_CASES])
+def test_act_vs_oracle_given_mean_sample(kind, O_, A, H, n, options):
     rng = np.random.default_rng(7)
-    ag = make_agent(kind, O_, A, H, n)
+    ag = make_agent(kind, O_, A, H, n, options=options)
     L = O.layout_init(kind, O_, A, H)
     p = random_params(L, rng)
     ag.load_params(p)
